@@ -1,6 +1,6 @@
 """Benchmark: aggregate env-steps/s of PandaReach at 4096 envs per GPU (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--dump-outputs DIR] [--full]
 
 One step = one batched env step of all envs on the GPU: device Philox random
 actions (pgx_sample_actions) + the fused IK/physics/obs/reward/auto-reset
@@ -9,9 +9,15 @@ driver launches one process per GPU (torch.distributed.run); envs are sharded
 by global id (rank r owns ids [r*E, (r+1)*E)), nothing is exchanged on the step
 path, and the timed region is bracketed by barriers with the max over ranks.
 
-Rank 0 prints one JSON line with the roofline of the step kernel (algorithmic
-bytes from SURVEY.md §8d over the HIP-event kernel time) and a CPU baseline
-(the fp64 oracle = CPU restatement, not PyBullet, timed on this host).
+A plain run sets up, warms up, times the K steps and rank 0 prints one JSON line with the
+headline (``value`` env-steps/s, ``ms_per_step``).  ``--dump-outputs DIR`` also writes what the
+last timed step returned to its caller (actions, obs, goals, reward, flags) as DIR/<name>.npy;
+with the same arguments the inputs, and so these arrays, are the same from run to run.
+
+``--full`` adds every other leg to that line: the roofline of the step kernel (algorithmic
+bytes from SURVEY.md §8d over the HIP-event kernel time), the HIP-graph replay, ReachAO, the
+Push / PickAndPlace / HER legs, the SB3 host path and a CPU baseline (the fp64 oracle = CPU
+restatement, not PyBullet, timed on this host).
 """
 import argparse
 import json
@@ -115,6 +121,11 @@ def parse():
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--env-id", default="PandaReach-v3")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (step-kernel time and rooflines, HIP-graph replay, ReachAO, "
+                         "Push / PickAndPlace, HER, SB3 host path, CPU baselines); the options below shape those legs")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-launches", type=int, default=200, help="launches for the kernel-time measurement")
@@ -443,6 +454,34 @@ def launch_ranks(n: int) -> int:
     return subprocess.call(cmd)
 
 
+DUMP_MAX_BYTES = 64 << 20   # cap of one --dump-outputs directory
+
+
+def dump_outputs(out_dir: str, venv, rank: int, world: int) -> None:
+    """``--dump-outputs DIR``: what the last timed step handed its caller -- the actions
+    sample_actions drew and step_tensors' obs dict, reward, terminated, truncated, success -- one
+    DIR/<name>.npy each (f32; the uint8 flags as 0.0 / 1.0), rows in env order.  Past the size cap
+    a fixed seeded sample of the envs is written, their indices in env_index.npy.  With several
+    ranks each writes its own shard as <name>.rank<r>.npy."""
+    obs = venv._obs_dict()
+    arrays = {"actions": venv._actions, "observation": obs["observation"], "achieved_goal": obs["achieved_goal"],
+              "desired_goal": obs["desired_goal"], "reward": venv.reward, "terminated": venv.terminated,
+              "truncated": venv.truncated, "success": venv.success}
+    n = venv.num_envs
+    row_bytes = sum(4 * t[0].numel() for t in arrays.values()) + 8
+    rows = None
+    if n * row_bytes * world > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (row_bytes * world)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f".rank{rank}" if world > 1 else ""
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a if rows is None else a[rows])
+    if rows is not None:
+        np.save(os.path.join(out_dir, "env_index" + sfx + ".npy"), rows.astype(np.float64))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -468,7 +507,7 @@ def main():
     coll_dev = dev if args.dist_backend == "nccl" else None   # where the collective tensors live
 
     import panda_gym_amd as pg
-    from panda_gym_amd.shard import gather_stats, max_over_ranks, shard_offset
+    from panda_gym_amd.shard import max_over_ranks, shard_offset
 
     E = args.envs
     venv = pg.PandaVecEnv(args.env_id, num_envs=E, device=dev, seed=args.seed,
@@ -495,11 +534,42 @@ def main():
     torch.cuda.synchronize(dev)
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, dist, coll_dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, venv, rank, world)
+    total = world * E * args.steps
+    line = {
+        "metric": "aggregate env-steps/s, PandaReach 4096 envs @1 GPU; 1/2/4/8-GPU scaling",
+        "value": total / elapsed, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "steady_state": f"episode phases staggered (env g starts its TimeLimit counter at g mod "
+                        f"{venv.spec.max_episode_steps}: every step auto-resets ~{E // venv.spec.max_episode_steps} "
+                        f"envs), timed after {venv.spec.max_episode_steps} + {args.warmup} untimed steps "
+                        f"(every env has auto-reset at least once)",
+        "kernel": kname,
+        "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic: device Philox random policy U[-1,1)^3, 50-step episodes with in-kernel auto-reset",
+        "config": {"workload": f"{args.env_id} (ee control, sparse reward), {E} envs per GPU, the "
+                               f"reference's scene: table / plane contacts of the robot (BASELINE configs[1])",
+                   "envs_per_gpu": E, "global_envs": world * E, "parallelism": f"env-sharded x{world}"},
+    }
+    if args.full:
+        line.update(full_legs(args, venv, dev, dist, rank, world, coll_dev, kname))
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    venv.close()
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def full_legs(args, venv, dev, dist, rank: int, world: int, coll_dev, kname: str) -> dict:
+    """``--full``: every leg beside the headline, run after it on the same handle; rank 0 gets the
+    fields they add to the result line (the other ranks an empty dict)."""
+    from panda_gym_amd.shard import gather_stats
+
+    E = venv.num_envs
     # episode statistics all-gather (outside the timed region; 16 B per rank over xGMI)
     stats = gather_stats([float(venv.truncated.sum()), float(venv.success.sum()), float(venv.reward.sum()),
                           float(args.steps)], dist, coll_dev).sum(0)
-    total = world * E * args.steps
-    value = total / elapsed
 
     # kernel time of pgx_step alone (HIP events on the launch stream = torch's current stream),
     # on the same random-policy workload: the actions are drawn up front
@@ -571,23 +641,10 @@ def main():
                                       "stall_split": prof.get("stall_split"),
                                       "source": os.path.relpath(PROFILE_JSON, ROOT)}
         line = {
-            "metric": "aggregate env-steps/s, PandaReach 4096 envs @1 GPU; 1/2/4/8-GPU scaling",
-            "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             # the step kernel alone: HIP events over --kernel-launches back-to-back launches on the launch
             # stream right after the timed window (launch gaps included; rocprof's kernel average,
             # profiles/, is the gap-free duration)
             "kernel_ms": kernel_ms,
-            "steady_state": f"episode phases staggered (env g starts its TimeLimit counter at g mod "
-                            f"{venv.spec.max_episode_steps}: every step auto-resets ~{E // venv.spec.max_episode_steps} "
-                            f"envs), timed after {venv.spec.max_episode_steps} + {args.warmup} untimed steps "
-                            f"(every env has auto-reset at least once)",
-            "kernel": kname,
-            "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic: device Philox random policy U[-1,1)^3, 50-step episodes with in-kernel auto-reset",
-            "config": {"workload": f"{args.env_id} (ee control, sparse reward), {E} envs per GPU, the "
-                                   f"reference's scene: table / plane contacts of the robot (BASELINE configs[1])",
-                       "envs_per_gpu": E, "global_envs": world * E, "parallelism": f"env-sharded x{world}"},
             # HBM is reported as the contract asks but does not bind this kernel: a step is ~200 B of
             # state against a long dependent VALU chain per env, so the
             # kernel is latency / VALU-issue bound; roofline_valu is the figure that measures it
@@ -621,10 +678,8 @@ def main():
                              task_leg(dev, "PandaPickAndPlace-v3", 16384, args.task_steps, flops_key="pick_and_place",
                                       full_manifold=False)]
             line["sb3_host_path"] = host_path_leg(dev, args.env_id, E, 100)
-        print(json.dumps(line), flush=True)
-    venv.close()
-    if dist is not None:
-        dist.destroy_process_group()
+        return line
+    return {}
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@ and every random draw (device Philox actions, auto-reset goals and obstacles) is
 global id, so a sharded run must equal the unsharded one env for env.  Checked here through the
 C-ABI (libpgx): eight 8192-env handles with offsets r*8192 against one 65536-env handle, every
 output of every step bit for bit over 30 steps with collisions, successes and resets; and the
-bench's own multi-rank launcher (``bench.py --gpus 2 --dist-backend gloo``: two ranks sharing the
+bench's own multi-rank launcher (``bench.py --full --gpus 2 --dist-backend gloo``: two ranks sharing the
 one GPU, gloo collectives on the host) against the single-rank run of the same global envs.
 """
 import json
@@ -73,12 +73,34 @@ def _bench(args, timeout=240):
     return json.loads(lines[0])
 
 
+def test_bench_plain_run_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """A plain run times --steps steps and reports the headline alone (no leg of --full); its
+    --dump-outputs arrays are f32, one row per env, and the same from run to run."""
+    import numpy as np
+
+    args = ["--gpus", "1", "--envs", "1000", "--steps", "7", "--warmup", "2"]
+    a = _bench(args + ["--dump-outputs", str(tmp_path / "a")])
+    _bench(args + ["--dump-outputs", str(tmp_path / "b")])
+    assert a["steps"] == 7 and a["ms_per_step"] > 0 and a["unit"] == "env-steps/s" and a["dtype"] == "f32"
+    assert a["value"] == pytest.approx(1000 / (a["ms_per_step"] * 1e-3))
+    for k in ("kernel_ms", "roofline", "graph_replay", "reach_ao", "cpu_baseline", "her_relabel", "tasks"):
+        assert k not in a, k
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(n + ".npy" for n in ("actions", "observation", "achieved_goal", "desired_goal", "reward",
+                                                "terminated", "truncated", "success"))
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and x.shape[0] == 1000 and np.isfinite(x).all(), n
+        assert np.array_equal(x, y), n
+    assert np.abs(np.load(tmp_path / "a" / "observation.npy")).max() > 0
+
+
 def test_bench_two_ranks_on_one_gpu_match_single_rank():
     """bench.py's launcher (a child torch.distributed.run job) with two gloo ranks on this one
     GPU: n_gpus 2, ReachAO global_envs 2 x 4096, and the final observations of every env equal
     the single-rank run of the same 8192 global envs (obs_digest)."""
-    common = ["--steps", "5", "--warmup", "2", "--task-steps", "30", "--no-cpu-baseline", "--no-her", "--no-tasks",
-              "--kernel-launches", "5"]
+    common = ["--full", "--steps", "5", "--warmup", "2", "--task-steps", "30", "--no-cpu-baseline", "--no-her",
+              "--no-tasks", "--kernel-launches", "5"]
     two = _bench(["--gpus", "2", "--dist-backend", "gloo", "--envs", "1024", "--ao-envs", "4096"] + common)
     one = _bench(["--gpus", "1", "--envs", "1024", "--ao-envs", "8192"] + common)
     assert two["n_gpus"] == 2 and two["config"]["global_envs"] == 2048
