@@ -2846,6 +2846,14 @@ constexpr bool limit_rows_paired() {
     return (PGX_N_ROWS - NJ) % 2 == 0;
 }
 
+/* the last motor row of the table (the first row of a reversed sweep without limit rows) */
+constexpr int last_motor_row() {
+    int r = 0;
+    for (int i = 0; i < PGX_N_ROWS; i++)
+        if ((kPgxRowCode[i] >> 4) == 0) r = i;
+    return r;
+}
+
 template <int OBJ, int CONT, int PART = 1, int AO = 0, int FULL = 0>
 __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q, float* qd, const float* tq,
                                           ObjState& ob, ContactLdsGT<OBJ, FULL>* Lp, int es, int c, const LaneK& K,
@@ -3304,6 +3312,27 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
     /* PKD (bit 2; the object tasks' full-manifold kernels, two Delassus registers, neither PKM nor
      * PKC): the pair is {gw, gw2} instead, coefficients {wms, wms2} / {Wc, Wc2} */
     constexpr bool PKD = TWO && FULL && !PKM && !PKC && (PK & 4) != 0;
+    /* MERGE (arm tasks, waves with at most 2 robot points and no extra points; the far, speculative
+     * and partial solves): the 7 + 6 rows' velocities in one register.  Lanes 0..6 of gv hold the
+     * dofs' deltas and lane 7 the partial solve's slot as ever; lane MG0 + q takes contact row q's
+     * x_q from gw, and lanes MG0.. of every row's coordinate column (mcs, cR) take its Delassus
+     * column (wms, Wc), so a row's update is one fma -- on each lane the fma the two registers
+     * did, bit for bit -- and a contact row reads lane MG0 + q.  gw, wms and Wc are dead through
+     * such sweeps; a redo with all rows splits the columns again (below).  The all-rows solve,
+     * the 4-point copies and the extra-point copies (their 16-lane reductions over gv) keep two
+     * registers. */
+    /* (not in the two-waves-per-SIMD build, PART 2: with the second instance of the limit-row solves
+     * its frame grows from 232 to 240 B of scratch per lane -- another whole-kernel value spilled at
+     * entry -- in every variant tried; it keeps the two-register sweeps) */
+    constexpr bool MERGE = WROWS && !OBJ && !AO && !PKM && !PKC && PART != 2;
+    constexpr int MG0 = 8;
+    static_assert(!MERGE || MG0 + 6 <= GW, "6 contact rows from lane MG0");
+    auto hi_sel = [&](float a, float other) __attribute__((always_inline)) {   /* lanes MG0.. take a */
+        float r;
+        asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(other), "v"(a), "s"(0xFF00FF00FF00FF00ull));
+        return r;
+    };
+    auto ror8 = [&](float v) __attribute__((always_inline)) { return dpp<0x128>(v); };   /* row_ror:8 */
     f2 mw[NJ], crw[NQ], mw2[NJ], cw2[NQ];
     /* motor rows: the shifted bound pair (lo' - lambda', hi' - lambda') tracked instead of
      * lambda', one v_pk_add_f32 per row update (lambda' itself is not needed after the solve:
@@ -3329,7 +3358,10 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
     init_bounds();
     /* G2 (g2_c): the second Delassus register holds live rows in this solve (rows 16.. exist:
      * robot points past the first in the object tasks); without them its updates are skipped */
-    auto mrow = [&](auto rc, auto g2_c, float& resid) __attribute__((always_inline)) {
+    /* (a row's |delta'| goes into the half-sweep's residual; mg_c = 2 marks the first row of a
+     * merged half-sweep, which starts the residual -- max(0, |d|) = |d| -- so that the 13 rows are
+     * six v_max3, without the and + max that open the chain otherwise) */
+    auto mrow = [&](auto rc, auto g2_c, auto mg_c, float& resid) __attribute__((always_inline)) {
         constexpr int r = decltype(rc)::value;
         constexpr int kind = kPgxRowCode[r] >> 4, d = kPgxRowCode[r] & 15;
         /* delta' = clamp(rhs' - s v_d, lo' - lambda', hi' - lambda'): the shifted bounds are
@@ -3354,7 +3386,9 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
             lam[r] += delta;
         }
         const float sd = kind == 2 ? -delta : delta;
-        if constexpr (PKD) {
+        if constexpr (decltype(mg_c)::value) {
+            gv += mcs[d] * sd;   /* merged: lanes 8.. of mcs hold the row's Delassus column */
+        } else if constexpr (PKD) {
             gv += mcs[d] * sd;
             if constexpr (decltype(g2_c)::value) pk_fma_acc(gw, gw2, mw2[d], sd);
             else gw += mw2[d].x * sd;
@@ -3367,7 +3401,8 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
             }
             if constexpr (TWO && decltype(g2_c)::value) gw2 += wms2[d] * sd;
         }
-        resid = fmaxf(resid, fabsf(delta));
+        if constexpr (decltype(mg_c)::value == 2) resid = fabsf(delta);
+        else resid = fmaxf(resid, fabsf(delta));
     };
     /* contact rows in scaled units too: lambda' = lambda den, friction bounds
      * +-mu lambda_n den_f = +-lambda'_n (mu jinv_n den_f); an idle row (inactive point, no
@@ -3449,7 +3484,7 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
         chi[p] = rok[p][0] ? 3.0e38f : 0.0f;
         if (WROWS && !rok[p][0]) clam[p][0] = 0.0f;   /* already applied to gv; the cache stores lambda' jinv = 0 */
     }
-    auto crow = [&](auto pc, auto dc, const bool fr, auto g2_c, float& resid) __attribute__((always_inline)) {
+    auto crow = [&](auto pc, auto dc, const bool fr, auto g2_c, auto mg_c, float& resid) __attribute__((always_inline)) {
         constexpr int p = decltype(pc)::value, dir = decltype(dc)::value, q = 3 * p + dir;
         const float ln_n = clam[p][0], lm = clam[p][dir];
         float lo, hi;
@@ -3464,10 +3499,14 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
             lo = -lm;
             hi = OBJ ? 3.0e38f : chi[p];
         }
-        const float x = q < GW ? bcast16<q % GW>(gw) : bcast16<q % GW>(gw2);   /* rhs' - w */
+        constexpr bool MG = decltype(mg_c)::value != 0;
+        const float x = MG ? bcast16<(MG0 + q) % GW>(gv)
+                           : (q < GW ? bcast16<q % GW>(gw) : bcast16<q % GW>(gw2));   /* rhs' - w */
         const float delta = __builtin_amdgcn_fmed3f(x, lo, hi);
         clam[p][dir] = lm + delta;
-        if constexpr (PKD) {
+        if constexpr (MG) {
+            gv += cR[p][dir] * delta;   /* merged: lanes 8.. of cR hold the row's Delassus column */
+        } else if constexpr (PKD) {
             gv += cR[p][dir] * delta;
             if constexpr (decltype(g2_c)::value) pk_fma_acc(gw, gw2, cw2[q], delta);
             else gw += cw2[q].x * delta;
@@ -3480,7 +3519,8 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
             }
             if constexpr (TWO && decltype(g2_c)::value) gw2 += Wc2[q] * delta;
         }
-        resid = fmaxf(resid, fabsf(delta));
+        if constexpr (decltype(mg_c)::value == 2) resid = fabsf(delta);
+        else resid = fmaxf(resid, fabsf(delta));
     };
     /* the wave's largest robot-point count, a scalar: the per-point branches in the sweep
      * are s_cmp on it (a per-point bool there turns into a VALU mask round trip per row) */
@@ -3562,14 +3602,14 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
             if constexpr (TWO && decltype(g2_c)::value) correct(IC<1>{}, gw2);
         }
     };
-    auto contact_rows = [&](auto nw_c, auto nx_c, auto g2_c, float& resid) __attribute__((always_inline)) {
+    auto contact_rows = [&](auto nw_c, auto nx_c, auto g2_c, auto mg_c, float& resid) __attribute__((always_inline)) {
         constexpr int NW = decltype(nw_c)::value;
 #pragma unroll
         for (int fr = 0; fr < 2; fr++) {
             if (OBJ && g0_any) {
                 sfor<0, P0>([&](auto kc) __attribute__((always_inline)) {
-                    if (fr) { crow(kc, IC<1>{}, true, g2_c, resid); crow(kc, IC<2>{}, true, g2_c, resid); }
-                    else crow(kc, IC<0>{}, false, g2_c, resid);
+                    if (fr) { crow(kc, IC<1>{}, true, g2_c, mg_c, resid); crow(kc, IC<2>{}, true, g2_c, mg_c, resid); }
+                    else crow(kc, IC<0>{}, false, g2_c, mg_c, resid);
                 });
             }
             if (NW < 0 && !g1_any) continue;
@@ -3577,10 +3617,10 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
                 constexpr int k = decltype(kc)::value;
                 if (NW >= 0 || k < n1w) {
                     if (fr) {
-                        crow(IC<P0 + k>{}, IC<1>{}, true, g2_c, resid);
-                        crow(IC<P0 + k>{}, IC<2>{}, true, g2_c, resid);
+                        crow(IC<P0 + k>{}, IC<1>{}, true, g2_c, mg_c, resid);
+                        crow(IC<P0 + k>{}, IC<2>{}, true, g2_c, mg_c, resid);
                     } else {
-                        crow(IC<P0 + k>{}, IC<0>{}, false, g2_c, resid);
+                        crow(IC<P0 + k>{}, IC<0>{}, false, g2_c, mg_c, resid);
                     }
                 }
             });
@@ -3624,64 +3664,75 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
      * bitwise the all-rows solve's. */
     constexpr int KMAX = CONT ? 1 : 2;   /* two slots measured -1.2 % without the table, +1 % with it */
     constexpr int SL0 = OBJ ? 13 : NJ;   /* first slot lane: the first lane past the coordinates */
+    static_assert(!MERGE || SL0 + KMAX <= MG0, "the slot lanes (mirror() writes SL0 .. SL0 + KMAX - 1) end below the merged contact lanes");
+    static_assert((kPgxRowCode[0] >> 4) == 0, "row 0 is a motor row (the first row of a forward sweep)");
     unsigned dmask = 0u;
     float smcs[KMAX], swms[KMAX], swms2[KMAX], srh[KMAX][2], slhi[KMAX], slam[KMAX][2];
     f2 smw[KMAX];   /* PKM: {smcs, swms} */
-    auto srow = [&](auto sc, auto kc, auto g2_c, float& resid) __attribute__((always_inline)) {
+    auto srow = [&](auto sc, auto kc, auto g2_c, auto mg_c, float& resid) __attribute__((always_inline)) {
         constexpr int S = decltype(sc)::value, KIND = decltype(kc)::value;   /* 1 lower, 2 upper */
         const float x = KIND == 2 ? srh[S][1] + bcast16<SL0 + S>(gv) : srh[S][0] - bcast16<SL0 + S>(gv);
         const float delta = __builtin_amdgcn_fmed3f(x, -slam[S][KIND - 1], slhi[S] - slam[S][KIND - 1]);
         slam[S][KIND - 1] += delta;
         const float sd = KIND == 2 ? -delta : delta;
-        if constexpr (PKM) {
+        if constexpr (decltype(mg_c)::value) {
+            gv += smcs[S] * sd;   /* merged: selected from the merged mcs */
+        } else if constexpr (PKM) {
             pk_fma_acc(gv, gw, smw[S], sd);
         } else {
             gv += smcs[S] * sd;
             if constexpr (WROWS) gw += swms[S] * sd;
         }
         if constexpr (TWO && decltype(g2_c)::value) gw2 += swms2[S] * sd;
-        resid = fmaxf(resid, fabsf(delta));
+        if constexpr (decltype(mg_c)::value == 2) resid = fabsf(delta);
+        else resid = fmaxf(resid, fabsf(delta));
     };
     static_assert(limit_rows_paired(), "limit rows come as (lower, upper) pairs of one dof after the motor rows");
-    auto solve = [&](auto mode_c, auto nw_c, auto k_c, auto nx_c) __attribute__((always_inline)) {
+    auto solve = [&](auto mode_c, auto nw_c, auto k_c, auto nx_c, auto mg_c) __attribute__((always_inline)) {
         constexpr int MODE = decltype(mode_c)::value;   /* 0 far, 1 speculative, 2 all rows, 3 partial */
         constexpr int NW = decltype(nw_c)::value;
         constexpr int K = decltype(k_c)::value;         /* MODE 3: slots in use */
         /* NX: extra robot points (past CGR) the sweep runs, 0 or a multiple of XSTEP */
         constexpr bool G2 = TWO && (NW < 0 || 3 * (P0 + NW) > GW);
         const IC<G2 ? 1 : 0> g2_c{};
+        constexpr bool MG = decltype(mg_c)::value != 0;
+        const IC<MG ? 2 : 0> mgf_c{};   /* the half-sweep's first row (res_acc) */
+        constexpr int LASTM = last_motor_row();
         for (int it = 0; it < n_it; it += 2) {
             float resid = 0.0f;
             if constexpr (MODE == 1 || MODE == 3) limit_check();
             if constexpr (MODE == 3) {   /* the limit block leads the reversed sweep */
                 sfor<0, K>([&](auto i) __attribute__((always_inline)) {
                     constexpr int S = K - 1 - decltype(i)::value;
-                    srow(IC<S>{}, IC<2>{}, g2_c, resid);
-                    srow(IC<S>{}, IC<1>{}, g2_c, resid);
+                    if constexpr (MG && S == K - 1) srow(IC<S>{}, IC<2>{}, g2_c, mgf_c, resid);
+                    else srow(IC<S>{}, IC<2>{}, g2_c, mg_c, resid);
+                    srow(IC<S>{}, IC<1>{}, g2_c, mg_c, resid);
                     limit_check();
                 });
             }
             sfor<0, PGX_N_ROWS>([&](auto i) __attribute__((always_inline)) {
                 constexpr int r = PGX_N_ROWS - 1 - decltype(i)::value;
-                if constexpr (MODE == 2 || (kPgxRowCode[r] >> 4) == 0) mrow(IC<r>{}, g2_c, resid);
+                if constexpr (MG && MODE != 3 && r == LASTM) mrow(IC<r>{}, g2_c, mgf_c, resid);
+                else if constexpr (MODE == 2 || (kPgxRowCode[r] >> 4) == 0) mrow(IC<r>{}, g2_c, mg_c, resid);
             });
-            if (CONT && (OBJ || NW > 0 || (NW < 0 && any_contact))) contact_rows(nw_c, nx_c, g2_c, resid);
+            if (CONT && (OBJ || NW > 0 || (NW < 0 && any_contact))) contact_rows(nw_c, nx_c, g2_c, mg_c, resid);
             PGX_PROF_SWEEP();
             if (resid <= res_thr || it + 1 >= n_it) break;
             resid = 0.0f;
             sfor<0, PGX_N_ROWS>([&](auto i) __attribute__((always_inline)) {
                 constexpr int r = decltype(i)::value;
-                if constexpr (MODE == 2 || (kPgxRowCode[r] >> 4) == 0) mrow(IC<r>{}, g2_c, resid);
+                if constexpr (MG && r == 0) mrow(IC<r>{}, g2_c, mgf_c, resid);
+                else if constexpr (MODE == 2 || (kPgxRowCode[r] >> 4) == 0) mrow(IC<r>{}, g2_c, mg_c, resid);
             });
             if constexpr (MODE == 1 || MODE == 3) limit_check();
             if constexpr (MODE == 3) {
                 sfor<0, K>([&](auto sc) __attribute__((always_inline)) {
-                    srow(sc, IC<1>{}, g2_c, resid);
-                    srow(sc, IC<2>{}, g2_c, resid);
+                    srow(sc, IC<1>{}, g2_c, mg_c, resid);
+                    srow(sc, IC<2>{}, g2_c, mg_c, resid);
                     limit_check();
                 });
             }
-            if (CONT && (OBJ || NW > 0 || (NW < 0 && any_contact))) contact_rows(nw_c, nx_c, g2_c, resid);
+            if (CONT && (OBJ || NW > 0 || (NW < 0 && any_contact))) contact_rows(nw_c, nx_c, g2_c, mg_c, resid);
             PGX_PROF_SWEEP();
             if (resid <= res_thr) break;
         }
@@ -3689,28 +3740,56 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
     /* the robot point count fixed at compile time (above) for every mode but far; the extra
      * points (past CGR) only in the speculative and all-rows solves (the partial one hands a wave
      * with extra points to the all-rows solve) */
-    auto solve_w = [&](auto mode_c, auto k_c) __attribute__((always_inline)) {
+    /* merged sweeps for this wave (MERGE, above): a wave-uniform choice outside the sweep loop;
+     * PGX_PGS_MODE=4 is "auto, but never merge" (the two-register sweeps, for A/B tests) */
+    const bool mg = MERGE && e.pgs_mode != 4 && n1w >= 1 && n1w <= 2 && nxr == 0;
+    auto merge_rows = [&]() __attribute__((always_inline)) {
+        if constexpr (MERGE) {
+#pragma unroll
+            for (int d = 0; d < NJ; d++) mcs[d] = hi_sel(ror8(wms[d]), mcs[d]);
+#pragma unroll
+            for (int q = 0; q < 6; q++) cR[q / 3][q % 3] = hi_sel(ror8(Wc[q]), cR[q / 3][q % 3]);
+            gv = hi_sel(ror8(gw), gv);
+        }
+    };
+    /* before an all-rows redo: the Delassus columns back in their own registers (rows 6.. are
+     * idle in a merged wave, their lanes zero; lanes MG0.. of mcs / cR / gv keep merged values,
+     * which the 2-point all-rows copy never reads) */
+    auto split_rows = [&]() __attribute__((always_inline)) {
+        if constexpr (MERGE) {
+#pragma unroll
+            for (int d = 0; d < NJ; d++) wms[d] = hi_sel(0.0f, ror8(mcs[d]));
+#pragma unroll
+            for (int q = 0; q < 6; q++) Wc[q] = hi_sel(0.0f, ror8(cR[q / 3][q % 3]));
+        }
+    };
+    /* (mgi_c: the merged wave's own instance of the solves -- 1 or 2 points, no extra points, so
+     * only the 2-point copies, and nothing of wms / Wc live through its sweeps) */
+    auto solve_w = [&](auto mode_c, auto k_c, auto mgi_c) __attribute__((always_inline)) {
         constexpr int MODE = decltype(mode_c)::value;
-        if constexpr (WROWS) {
+        const IC<0> m0{};
+        if constexpr (decltype(mgi_c)::value) {
+            solve(mode_c, IC<2>{}, k_c, IC<0>{}, IC<(MODE != 2) ? 1 : 0>{});
+        } else if constexpr (WROWS) {
             /* (n1w counts register points only: a wave with extra points has n1w = CGR, which is 2
              * for the arm tasks, so the extra-point copies are chosen by nxr first) */
-            if (n1w == 0) solve(mode_c, IC<0>{}, k_c, IC<0>{});
-            else if (nxr == 0 && n1w <= 2) solve(mode_c, IC<2>{}, k_c, IC<0>{});
-            else if (CGR > 4 && nxr == 0 && n1w <= 4) solve(mode_c, IC<(CGR > 4 ? 4 : CGR)>{}, k_c, IC<0>{});
+            if (n1w == 0) solve(mode_c, IC<0>{}, k_c, IC<0>{}, m0);
+            else if (nxr == 0 && n1w <= 2) solve(mode_c, IC<2>{}, k_c, IC<0>{}, m0);
+            else if (CGR > 4 && nxr == 0 && n1w <= 4) solve(mode_c, IC<(CGR > 4 ? 4 : CGR)>{}, k_c, IC<0>{}, m0);
             else if constexpr (RB > CGR && MODE != 3) {
                 if (nxr == 0) {
-                    solve(mode_c, IC<CGR>{}, k_c, IC<0>{});
+                    solve(mode_c, IC<CGR>{}, k_c, IC<0>{}, m0);
                 } else {   /* one sweep copy per multiple of XSTEP (the wave's count rounded up) */
                     sfor<1, (RB - CGR) / XSTEP + 1>([&](auto ic) __attribute__((always_inline)) {
                         constexpr int NXC = decltype(ic)::value * XSTEP;
-                        if (nxr == NXC) solve(mode_c, IC<CGR>{}, k_c, IC<NXC>{});
+                        if (nxr == NXC) solve(mode_c, IC<CGR>{}, k_c, IC<NXC>{}, m0);
                     });
                 }
             } else {
-                solve(mode_c, IC<CGR>{}, k_c, IC<0>{});
+                solve(mode_c, IC<CGR>{}, k_c, IC<0>{}, m0);
             }
         } else {
-            solve(mode_c, IC<-1>{}, k_c, IC<0>{});
+            solve(mode_c, IC<-1>{}, k_c, IC<0>{}, m0);
         }
     };
     /* PARK_SOLVE: the state read only after the solve waits in LDS through the sweeps (relaxed
@@ -3738,7 +3817,7 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
         }
     }
     if (__all(far)) {   /* (far implies no robot point in the wave) */
-        solve(IC<0>{}, IC<0>{}, IC<0>{}, IC<0>{});
+        solve(IC<0>{}, IC<0>{}, IC<0>{}, IC<0>{}, IC<0>{});
     } else {
         PGX_PROF_COUNT(10, 1);
         init_limit_rows();
@@ -3769,98 +3848,21 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
 #pragma unroll
                 for (int p = 0; p < NP; p++) Lp->pl0[p][es] = clam[p][0];
             }
-            if (PART && !NO_PART && !spec_all && nk <= KMAX && nxr == 0) {   /* (NO_PART: all rows instead, fewer registers) */
-                PGX_PROF_COUNT(7, 1);
-                /* slots in the pairs' table order; slot lane SL0 + S mirrors dof d_S */
-                int ds[2] = {0, 0};
-                int k = 0;
-                sfor<0, (PGX_N_ROWS - NJ) / 2>([&](auto pc) __attribute__((always_inline)) {
-                    constexpr int d = kPgxRowCode[NJ + 2 * decltype(pc)::value] & 15;
-                    if ((dmask >> d) & 1u) { if (k == 0) ds[0] = d; else ds[1] = d; k++; }
-                });
-                ds[0] = __builtin_amdgcn_readfirstlane(ds[0]);
-                ds[1] = __builtin_amdgcn_readfirstlane(ds[1]);
-                const int src = (int)(threadIdx.x & ~(unsigned)(GW - 1));
-                auto mirror = [&](float& x) __attribute__((always_inline)) {
-                    x = lane_sel<SL0>(__shfl(x, src + ds[0]), x);
-                    if (KMAX > 1 && nk > 1) x = lane_sel<SL0 + 1>(__shfl(x, src + ds[1]), x);
+            /* the limit-row solves (pgx_limit_solves.inc): in the arm kernels one instance for merged
+             * waves (MGI) and one for the others; elsewhere in place */
+            if constexpr (MERGE) {
+                auto limit_solves = [&](auto mgi_c) __attribute__((always_inline)) {
+#include "pgx_limit_solves.inc"
                 };
-#pragma unroll
-                for (int d = 0; d < NJ; d++) {
-                    if constexpr (PKM) {   /* (mcs / cR live on only as the pairs' halves) */
-                        float t = mw[d].x;
-                        mirror(t);
-                        mw[d].x = t;
-                    } else {
-                        mirror(mcs[d]);
-                    }
-                }
-                mirror(gv);
-                if (g1_any) {
-#pragma unroll
-                    for (int p = 0; p < NP; p++)
-#pragma unroll
-                        for (int dir = 0; dir < 3; dir++) {
-                            if constexpr (PKC) {
-                                float t = crw[3 * p + dir].x;
-                                mirror(t);
-                                crw[3 * p + dir].x = t;
-                            } else {
-                                mirror(cR[p][dir]);
-                            }
-                        }
-                }
-                /* the slots' row data: dof d_S's entries, selected with uniform masks */
-#pragma unroll
-                for (int S = 0; S < KMAX; S++) {
-                    if constexpr (PKM) smw[S] = mw[0];
-                    else { smcs[S] = mcs[0]; swms[S] = PKD ? mw2[0].x : wms[0]; }
-                    swms2[S] = PKD ? mw2[0].y : wms2[0]; slhi[S] = lhi[0];
-                    srh[S][0] = rl[0]; srh[S][1] = ru[0];
-                    slam[S][0] = 0.0f; slam[S][1] = 0.0f;
-                    sfor<1, NJ>([&](auto dc) __attribute__((always_inline)) {
-                        constexpr int d = decltype(dc)::value;
-                        const bool hit = ds[S] == d;   /* wave-uniform */
-                        auto sel = [&](float a, float o) __attribute__((always_inline)) { return hit ? a : o; };
-                        if constexpr (PKM) smw[S] = hit ? mw[d] : smw[S];
-                        else { smcs[S] = sel(mcs[d], smcs[S]); swms[S] = sel(PKD ? mw2[d].x : wms[d], swms[S]); }
-                        swms2[S] = sel(PKD ? mw2[d].y : wms2[d], swms2[S]);
-                        slhi[S] = sel(lhi[d], slhi[S]);
-                        srh[S][0] = sel(rl[d], srh[S][0]); srh[S][1] = sel(ru[d], srh[S][1]);
-                    });
-                }
-                /* the checks skip the running dofs and the slot lanes */
-                if ((dmask >> c) & 1u) { rl_c = -3.0e38f; ru_c = -3.0e38f; }
-                if (c == SL0) rcol = ds[0];
-                if (KMAX > 1 && nk > 1 && c == SL0 + 1) rcol = ds[1];
-                PGX_PROF_COUNT(16, nk == 2 ? 1 : 0);
-                PGX_PROF_COUNT(18, any_contact ? 1 : 0);
-                if (KMAX == 1 || nk == 1) solve_w(IC<3>{}, IC<1>{});
-                else solve_w(IC<3>{}, IC<KMAX>{});
-            } else if (spec_all) {
-                solve_w(IC<1>{}, IC<0>{});
+                if (mg) limit_solves(IC<1>{});
+                else limit_solves(IC<0>{});
             } else {
-                lmargin = -1.0f;   /* more than KMAX dofs: all rows */
-            }
-            const bool viol = lmargin < 0.0f;
-            if (__any(row_any(viol)) || e.pgs_mode == 3) {
-                PGX_PROF_COUNT(12, 1);
-                gv = gv0;
-                gw = gw0;
-                gw2 = gw20;
-#pragma unroll
-                for (int p = 0; p < NP; p++) {
-                    clam[p][0] = CONT ? Lp->pl0[p][es] : 0.0f;
-                    clam[p][1] = 0.0f;
-                    clam[p][2] = 0.0f;
-                }
-                if (RB > CGR && nxr > 0) load_xs(false);
-                init_bounds();
-                solve_w(IC<2>{}, IC<0>{});
+                const IC<0> mgi_c{};
+#include "pgx_limit_solves.inc"
             }
         } else {
             PGX_PROF_COUNT(13, 1);
-            solve_w(IC<2>{}, IC<0>{});
+            solve_w(IC<2>{}, IC<0>{}, IC<0>{});
         }
     }
     PGX_PROF_SWEEPS_DONE();
