@@ -225,7 +225,15 @@ typedef struct pgx_config {
                                      finished episode); 1: it keeps its final state until
                                      pgx_reset, like one gymnasium env (RobotTaskEnv + TimeLimit,
                                      core.py:352-368) */
-    int32_t pad1;
+    int32_t nonfinite_guard;      /* 0: off.  1: the step checks every float it is about to store for an
+                                     env (q, qd, the cached pose, the object, the EE state, the goal
+                                     distance, ReachAO's link observation); an env with a NaN / inf among
+                                     them sets PGX_ERR_NONFINITE and pgx_step_out.nonfinite, reports
+                                     reward 0, success = terminated = task_truncated = 0, truncated = 1,
+                                     and -- unless no_auto_reset -- is reset in the same step like a
+                                     TimeLimit truncation (the cube's velocity, which that reset keeps,
+                                     zeroed), its terminal_* rows equal to its reset obs / goals.  Envs
+                                     without one are bit for bit what they are with 0 */
     uint64_t seed;                /* device Philox key for auto-reset draws */
     uint64_t env_id_offset;       /* global id of env 0 (multi-GPU sharding) */
     double base_pos[3];           /* robot base (-0.6,0,0) (panda_tasks.py:85) */
@@ -298,6 +306,9 @@ typedef struct pgx_step_out {
     uint8_t* task_truncated;      /* [N] u8 Task.is_truncated of the step (ReachAO: is_collided,
                                      reach_ao.py:1263-1264; 0 for the other tasks, reach.py:53-54),
                                      i.e. info["is_truncated"], without the TimeLimit part */
+    uint8_t* nonfinite;           /* [N] u8 written by pgx_step only: 1 for an env the non-finite guard
+                                     (pgx_config.nonfinite_guard) caught in this step, else 0; all 0
+                                     from a handle without the guard */
 } pgx_step_out;
 
 /* Device-resident state views (SoA, env-minor: x[k*N + env]). */
@@ -329,6 +340,9 @@ typedef struct pgx_state_view {
  * ("Couldn't find collision free obstacle!", reach_ao.py:1143-1145); the env keeps the last
  * draw and the host raises PgxError when it reads the bit. */
 #define PGX_ERR_AO_OBSTACLE 1u
+/* PGX_ERR_NONFINITE: the non-finite guard (pgx_config.nonfinite_guard) caught an env in some step
+ * since the host last cleared the word; pgx_step_out.nonfinite names the envs of each step. */
+#define PGX_ERR_NONFINITE 2u
 
 const char* pgx_version(void);
 const char* pgx_last_error(void);

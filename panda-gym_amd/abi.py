@@ -86,7 +86,7 @@ class PgxConfig(C.Structure):
     _fields_ = [
         ("task", C.c_int32), ("control", C.c_int32), ("reward", C.c_int32), ("n_envs", C.c_int32),
         ("max_episode_steps", C.c_int32), ("block_gripper", C.c_int32), ("no_auto_reset", C.c_int32),
-        ("pad1", C.c_int32), ("seed", C.c_uint64), ("env_id_offset", C.c_uint64),
+        ("nonfinite_guard", C.c_int32), ("seed", C.c_uint64), ("env_id_offset", C.c_uint64),
         ("base_pos", C.c_double * 3), ("distance_threshold", C.c_double),
         ("goal_low", C.c_double * 3), ("goal_high", C.c_double * 3),
         ("joint_forces", C.c_double * MAX_DOFS), ("neutral_q", C.c_double * MAX_DOFS),
@@ -104,6 +104,7 @@ class PgxConfig(C.Structure):
 
 
 ERR_AO_OBSTACLE = 1   # PGX_ERR_AO_OBSTACLE (include/pgx.h): pgx_state_view.errors bit
+ERR_NONFINITE = 2     # PGX_ERR_NONFINITE: the non-finite guard (PgxConfig.nonfinite_guard) caught an env
 
 
 class PgxStepOut(C.Structure):
@@ -111,7 +112,7 @@ class PgxStepOut(C.Structure):
         ("obs", C.c_void_p), ("achieved_goal", C.c_void_p), ("desired_goal", C.c_void_p),
         ("reward", C.c_void_p), ("success", C.c_void_p), ("terminated", C.c_void_p),
         ("truncated", C.c_void_p), ("terminal_obs", C.c_void_p), ("terminal_achieved_goal", C.c_void_p),
-        ("terminal_desired_goal", C.c_void_p), ("task_truncated", C.c_void_p),
+        ("terminal_desired_goal", C.c_void_p), ("task_truncated", C.c_void_p), ("nonfinite", C.c_void_p),
     ]
 
 

@@ -500,6 +500,7 @@ int pgx_create(const pgx_config* cfg, int device, pgx_handle* out) {
     e.ao = cfg->task == PGX_TASK_REACH_AO;
     e.terminate_on_success = cfg->terminate_on_success ? 1 : 0;
     e.no_auto_reset = cfg->no_auto_reset ? 1 : 0;
+    e.nonfinite_guard = cfg->nonfinite_guard ? 1 : 0;
     e.collision_reward = cfg->collision_reward;
     for (int k = 0; k < 3; k++) e.ao_ee[k] = cfg->ao_ee_neutral[k];
     e.ao_ee_set = (cfg->ao_ee_neutral[0] != 0.0 || cfg->ao_ee_neutral[1] != 0.0 || cfg->ao_ee_neutral[2] != 0.0) ? 1 : 0;
@@ -669,8 +670,12 @@ int pgx_reset(pgx_handle h, const uint8_t* env_mask, const double* inject_goal, 
 
 int pgx_step(pgx_handle h, const float* action, pgx_step_out* out, void* stream) {
     if (!h || !action) return fail(PGX_E_INVALID, "null argument");
+    if (out && out->nonfinite && !h->de.nonfinite_guard) {   /* no guard, nothing caught: the kernels do not write it */
+        const int rc = hip_check((hipError_t)pgx_launch_zero_flags(out->nonfinite, h->de.n_envs, stream), "flags launch");
+        if (rc) return rc;
+    }
     return hip_check((hipError_t)pgx_launch_step(h->dm_dev, h->de, h->ds, action, to_dev_out(out), stream,
-                                                 &h->step_kernel),
+                                                 &h->step_kernel, out ? out->nonfinite : nullptr),
                      "step launch");
 }
 

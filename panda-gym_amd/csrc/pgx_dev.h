@@ -101,6 +101,7 @@ struct PgxDevEnv {
     int32_t sort_segs;             /* PGX_SORT_SEGS: 0 auto (8 per-XCD segments when N divides), 1 one global order */
     const int32_t* perm;
     int32_t perm_segs;             /* the launch's segments: 8 = perm is heavy-first within each XCD's env range */
+    int32_t nonfinite_guard;       /* pgx_config.nonfinite_guard: the launchers pick the step kernels' _nf builds */
 };
 
 struct PgxDevState {
@@ -134,17 +135,28 @@ struct PgxDevOut {
 /* launchers (pgx_kernels.hip); return hipError_t as int */
 /* the arm-only (Reach) step kernels: their own translation unit (pgx_kernels.hip, PGX_TU) */
 /* name (may be NULL): set to the launched step kernel's name, as rocprof spells it */
+/* nonfinite: pgx_step_out.nonfinite, an argument of the guarded (_nf) kernels alone (e.nonfinite_guard)
+ * -- PgxDevOut, and with it the kernels of a handle without the guard, stay as they were */
 int pgx_launch_step_arm(const PgxDevModel* m_device, const PgxDevEnv& e, const PgxDevState& s, const float* action,
-                        const PgxDevOut& o, void* stream, const char** name);
+                        const PgxDevOut& o, void* stream, const char** name, uint8_t* nonfinite);
 int pgx_launch_step(const PgxDevModel* m_device, const PgxDevEnv& e, const PgxDevState& s, const float* action,
-                    const PgxDevOut& o, void* stream, const char** name);
+                    const PgxDevOut& o, void* stream, const char** name, uint8_t* nonfinite);
 /* the ReachAO step kernels: their own translation unit too (PGX_TU 4, scheduler flags of its own);
  * e as pgx_launch_step hands it on (perm set), two: the two-wave build, wide: the 16-lane layout */
 int pgx_launch_step_ao(const PgxDevModel* m_device, const PgxDevEnv& e, const PgxDevState& s, const float* action,
-                       const PgxDevOut& o, void* stream, const char** name, bool two, bool wide);
+                       const PgxDevOut& o, void* stream, const char** name, bool two, bool wide, uint8_t* nonfinite);
+/* the same three for a handle with the non-finite guard (e.nonfinite_guard): the guarded kernels'
+ * own units (pgx_kernels.hip, PGX_NF), reached through pgx_launch_step */
+int pgx_launch_step_arm_nf(const PgxDevModel* m_device, const PgxDevEnv& e, const PgxDevState& s, const float* action,
+                           const PgxDevOut& o, void* stream, const char** name, uint8_t* nonfinite);
+int pgx_launch_step_nf(const PgxDevModel* m_device, const PgxDevEnv& e, const PgxDevState& s, const float* action,
+                       const PgxDevOut& o, void* stream, const char** name, uint8_t* nonfinite);
+int pgx_launch_step_ao_nf(const PgxDevModel* m_device, const PgxDevEnv& e, const PgxDevState& s, const float* action,
+                          const PgxDevOut& o, void* stream, const char** name, bool two, bool wide, uint8_t* nonfinite);
 int pgx_launch_reset(const PgxDevModel* m_device, const PgxDevEnv& e, const PgxDevState& s, const uint8_t* mask,
                      const double* inject_goal, const double* inject_object, const PgxDevOut& o, void* stream);
 int pgx_launch_sample_actions(const PgxDevEnv& e, float* action, uint64_t step, void* stream);
 int pgx_launch_set_word(int32_t* p, int32_t v, void* stream);
+int pgx_launch_zero_flags(uint8_t* p, int n, void* stream);
 int pgx_launch_compute_reward(const float* ag, const float* dg, int64_t n, int32_t reward_type, double thr,
                               float* out, void* stream);

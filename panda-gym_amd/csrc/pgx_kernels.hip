@@ -154,6 +154,10 @@ __device__ __forceinline__ V3 cross(V3 a, V3 b) {
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float fast_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 __device__ __forceinline__ float norm(V3 a) { return fast_sqrt(dot(a, a)); }
+/* (class compares, v_cmp_class_f32: no arithmetic a fast-math flag could fold away) */
+__device__ __forceinline__ bool finite3(V3 a) {
+    return __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z);
+}
 
 /* sin/cos of a joint angle (|x| < ~1e3): Cody-Waite reduction by pi/2 in three parts and
  * the Cephes single-precision minimax polynomials on [-pi/4, pi/4] (~1 ulp).  Branch-free
@@ -4637,9 +4641,13 @@ __device__ __forceinline__ int xcd_block() {
 
 /* WIDE = 0: one env per lane (64 per wave); WIDE = 1: 16 lanes per env (4 per wave,
  * substep_g), the redundant lanes compute the same values and only the lead lane stores. */
-template <int CONTROL, int OBJ, int CONT, int AO, int WIDE, int PART = 1>
+/* GUARD = 1 (pgx_config.nonfinite_guard, the step_kernel_nf builds): the non-finite guard, on entry
+ * and in the epilogue; GUARD = 0 compiles none of it, so a handle without the guard launches the
+ * kernels as they were before it existed. */
+template <int CONTROL, int OBJ, int CONT, int AO, int WIDE, int PART = 1, int GUARD = 0>
 __device__ __forceinline__ void step_body(const PgxDevModel* __restrict__ mdev, const PgxDevEnv& e,
-                                          const PgxDevState& s, const float* __restrict__ action, const PgxDevOut& o) {
+                                          const PgxDevState& s, const float* __restrict__ action, const PgxDevOut& o,
+                                          uint8_t* nf_out = nullptr) {
     /* WIDE: 0 one lane per env, 1 sixteen, 2 sixteen with the full manifold budget */
     constexpr int FULL = WIDE == 2 ? 1 : 0;
     using LT = ContactLdsT<WIDE ? EPW : 64, WIDE ? OBJ : 1, FULL>;
@@ -4757,6 +4765,21 @@ __device__ __forceinline__ void step_body(const PgxDevModel* __restrict__ mdev, 
         }
     }
 
+    /* the non-finite guard, on entry: the state as loaded and the motor targets (the cached pose
+     * and the action reach the step through them).  Not only the epilogue's values: the substeps
+     * clamp the joint velocities to +-max_coord_vel with fminf / fmaxf, which return their other
+     * operand for a NaN, so a NaN velocity leaves the step as a finite +-100 rad/s */
+    bool bad_in = false;
+    if constexpr (GUARD) {
+        bool fin = true;
+#pragma unroll
+        for (int j = 0; j < NJ; j++)
+            fin = fin && __builtin_isfinite(q[j]) && __builtin_isfinite(qd[j]) && __builtin_isfinite(tq[j]);
+        if constexpr (OBJ)
+            fin = fin && finite3(ob.p) && finite3(ob.v) && finite3(ob.w) && __builtin_isfinite(ob.qx) &&
+                  __builtin_isfinite(ob.qy) && __builtin_isfinite(ob.qz) && __builtin_isfinite(ob.qw);
+        bad_in = !fin;
+    }
     PGX_PROF_MARK(0);
     LaneK lk;
     if constexpr (WIDE) lane_consts(lk);
@@ -4874,8 +4897,45 @@ __device__ __forceinline__ void step_body(const PgxDevModel* __restrict__ mdev, 
     int el = s.elapsed[ie] + 1;
     uint32_t episode = s.episode[ie];
     /* TimeLimit, ReachAO.is_truncated (collision); terminate_on_success (core.py:359-361) */
-    const bool trunc = (e.max_episode_steps > 0 && el >= e.max_episode_steps) || collided;
-    const bool term = e.terminate_on_success && succ;
+    bool trunc = (e.max_episode_steps > 0 && el >= e.max_episode_steps) || collided;
+    bool term = e.terminate_on_success && succ;
+    /* The non-finite guard (pgx_config.nonfinite_guard; DESIGN.md section 4 "Non-finite guard"): what
+     * the step loaded (bad_in, above) and every float this epilogue is about to store for the env --
+     * q, qd, the link cache's pose, the cube's 13 values, the EE position / velocity, the fp64 goal
+     * distance (so the goal too), ReachAO's per-link distances and directions -- by class compares,
+     * not arithmetic.  A caught env (`bad`) reports a fixed, finite step (reward 0, truncated alone
+     * set) and takes the auto-reset branch below like a TimeLimit truncation; its terminal rows are
+     * written after the reset.  The decision is uniform over the env's row (a ballot), so the row's
+     * other lanes take the same branches. */
+    bool bad = false;
+    if constexpr (GUARD) {
+        if constexpr (AO) {   /* (the guard reads the link observation: before the decision) */
+            if constexpr (WIDE) ao_link_obs_g(*L, ln, c);
+            else ao_link_obs(*L, ln);
+        }
+        bool fin = __builtin_isfinite(d) && finite3(pos) && finite3(vel);
+#pragma unroll
+        for (int j = 0; j < NJ; j++)
+            fin = fin && __builtin_isfinite(q[j]) && __builtin_isfinite(qd[j]) && __builtin_isfinite(qprev[j]);
+        if constexpr (OBJ)
+            fin = fin && finite3(ob.p) && finite3(ob.v) && finite3(ob.w) && __builtin_isfinite(ob.qx) &&
+                  __builtin_isfinite(ob.qy) && __builtin_isfinite(ob.qz) && __builtin_isfinite(ob.qw);
+        if constexpr (AO) {
+#pragma unroll
+            for (int l = 0; l < PGX_AO_LINKS; l++)
+                fin = fin && __builtin_isfinite(L->aoD[l][ln]) && __builtin_isfinite(L->aoU[l][0][ln]) &&
+                      __builtin_isfinite(L->aoU[l][1][ln]) && __builtin_isfinite(L->aoU[l][2][ln]);
+        }
+        bad = !fin || bad_in;
+        if constexpr (WIDE) bad = row_any(bad);
+        if (bad) {
+            rew = 0.0f;
+            succ = false; term = false; collided = false;
+            trunc = true;
+            if (lead) atomicOr(s.errors, PGX_ERR_NONFINITE);
+        }
+        if (lead && nf_out) nf_out[ie] = bad;
+    }
     if (lead) {
         if (o.reward) o.reward[ie] = rew;
         if (o.success) o.success[ie] = succ;
@@ -4883,11 +4943,11 @@ __device__ __forceinline__ void step_body(const PgxDevModel* __restrict__ mdev, 
         if (o.truncated) o.truncated[ie] = trunc;
         if (o.task_truncated) o.task_truncated[ie] = collided;
     }
-    if constexpr (AO) {
+    if constexpr (AO && !GUARD) {
         if constexpr (WIDE) ao_link_obs_g(*L, ln, c);
         else ao_link_obs(*L, ln);
     }
-    if (trunc || term) {
+    if ((trunc || term) && !bad) {   /* (a caught env's rows: after its reset, with the outputs) */
         if (o.terminal_obs && lead) {
             if constexpr (AO) ao_write_obs(o.terminal_obs + (size_t)ie * od, pos, vel, q, qd, *L, ln);
             else write_obs<OBJ>(e, o.terminal_obs + (size_t)ie * od, pos, vel, ob);
@@ -4920,6 +4980,11 @@ __device__ __forceinline__ void step_body(const PgxDevModel* __restrict__ mdev, 
             else ao_link_obs(*L, ln);
         } else {
             reset_env<OBJ>(m, e, ie, episode, nullptr, nullptr, q, qd, goal, ob, lead);
+            /* the reset keeps the cube's velocity (resetBasePositionAndOrientation); a caught env's
+             * is not fit to keep: at rest */
+            if constexpr (GUARD && OBJ) {
+                if (bad) { ob.v = v3(0.0f, 0.0f, 0.0f); ob.w = v3(0.0f, 0.0f, 0.0f); }
+            }
             ee_state(m, q, qd, pos, vel);
 #pragma unroll
             for (int j = 0; j < NJ; j++) qprev[j] = q[j];   /* resetJointState refreshes the link cache */
@@ -4960,6 +5025,24 @@ __device__ __forceinline__ void step_body(const PgxDevModel* __restrict__ mdev, 
     if (o.dg) {
         o.dg[3 * (size_t)ie] = (float)goal[0]; o.dg[3 * (size_t)ie + 1] = (float)goal[1];
         o.dg[3 * (size_t)ie + 2] = (float)goal[2];
+    }
+    if constexpr (GUARD) {
+        /* a caught env that was reset: its terminal rows are the reset's (finite, and consistent with
+         * obs: a learner that stores next_obs = terminal_observation stores the new episode's start) */
+        if (bad && !e.no_auto_reset) {
+            if (o.terminal_obs) {
+                if constexpr (AO) ao_write_obs(o.terminal_obs + (size_t)ie * od, pos, vel, q, qd, *L, ln);
+                else write_obs<OBJ>(e, o.terminal_obs + (size_t)ie * od, pos, vel, ob);
+            }
+            if (o.terminal_ag) {
+                o.terminal_ag[3 * (size_t)ie] = ag2.x; o.terminal_ag[3 * (size_t)ie + 1] = ag2.y;
+                o.terminal_ag[3 * (size_t)ie + 2] = ag2.z;
+            }
+            if (o.terminal_dg) {
+                o.terminal_dg[3 * (size_t)ie] = (float)goal[0]; o.terminal_dg[3 * (size_t)ie + 1] = (float)goal[1];
+                o.terminal_dg[3 * (size_t)ie + 2] = (float)goal[2];
+            }
+        }
     }
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
@@ -5018,6 +5101,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     scene_from_model<AO>(e, mdev);
     step_body<CONTROL, OBJ, CONT, AO, WIDE, AO ? 0 : 2>(mdev, e, s, action, o);
 }
+/* the same two with the non-finite guard in the epilogue (pgx_config.nonfinite_guard) */
+template <int CONTROL, int OBJ, int CONT, int AO, int WIDE>
+__global__ __launch_bounds__(64) void step_kernel_nf(const PgxDevModel* __restrict__ mdev, PgxDevEnv e, PgxDevState s,
+                                                     const float* __restrict__ action, PgxDevOut o, uint8_t* nf) {
+    scene_from_model<AO>(e, mdev);
+    step_body<CONTROL, OBJ, CONT, AO, WIDE, 1, 1>(mdev, e, s, action, o, nf);
+}
+template <int CONTROL, int OBJ, int CONT, int AO, int WIDE>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void step_kernel_o2_nf(
+    const PgxDevModel* __restrict__ mdev, PgxDevEnv e, PgxDevState s, const float* __restrict__ action, PgxDevOut o,
+    uint8_t* nf) {
+    scene_from_model<AO>(e, mdev);
+    step_body<CONTROL, OBJ, CONT, AO, WIDE, AO ? 0 : 2, 1>(mdev, e, s, action, o, nf);
+}
 
 template <int OBJ, int AO>
 __global__ __launch_bounds__(64) void reset_kernel(const PgxDevModel* __restrict__ mdev, PgxDevEnv e, PgxDevState s,
@@ -5056,6 +5153,14 @@ __global__ __launch_bounds__(64) void reset_kernel(const PgxDevModel* __restrict
     } else {
         reset_env<OBJ>(m, e, i, episode, inject_goal ? inject_goal + 3 * (size_t)i : nullptr,
                        inject_obj ? inject_obj + 3 * (size_t)i : nullptr, q, qd, goal, ob);
+        /* the reset keeps the cube's velocity; with the non-finite guard on, not one that is NaN / inf
+         * (the host's reset of an env the guard caught on a no_auto_reset handle): at rest */
+        if constexpr (OBJ) {
+            if (e.nonfinite_guard && !(finite3(ob.v) && finite3(ob.w))) {
+                ob.v = v3(0.0f, 0.0f, 0.0f);
+                ob.w = v3(0.0f, 0.0f, 0.0f);
+            }
+        }
         ee_state(m, q, qd, pos, vel);
     }
     const V3 ag = OBJ ? ob.p : pos;
@@ -5249,6 +5354,37 @@ __global__ __launch_bounds__(SORT_SEG_MAX) void env_sort_segment_kernel(PgxDevSt
 #endif
 /* every launch names its kernel (rocprof's spelling) in *name: the label bench.py reports */
 #define PGX_KNAME(K, C, O, T, A, W) #K "<" #C ", " #O ", " #T ", " #A ", " #W ">"
+/* PGX_NF = 1: a unit of the guarded step kernels alone (step_kernel_nf / step_kernel_o2_nf, the
+ * non-finite guard in the epilogue) and their launchers, pgx_launch_step*_nf, which pgx_launch_step
+ * hands a guarded handle (e.nonfinite_guard) to -- one such unit beside each of the units 1, 2
+ * and 4, built with that unit's flags.  Units of their own, because in one module with their
+ * twins they change the twins' code: the inliner weighs a function by the number of its call
+ * sites in the module, and the two-wave Reach kernel and the one-lane ReachAO kernel came out
+ * with other inlining and register allocation.  Split, every kernel a handle without the guard
+ * launches is instruction for instruction what it was before the guard existed.  The profiling
+ * and debug builds (PGX_TU 0, -DPGX_NO_NF) have no guarded kernels: a guarded handle's step
+ * fails there with hipErrorNotSupported. */
+#ifndef PGX_NF
+#define PGX_NF 0
+#endif
+#if PGX_NF
+#define PGX_FN(f) f##_nf
+#define PGX_STEP(C, O, K, A, W)                                                                              \
+    do {                                                                                                     \
+        hipLaunchKernelGGL((step_kernel_nf<C, O, K, A, W>), grid, block, 0, st, m, e, s, action, o, nf);     \
+        if (name) *name = PGX_KNAME(step_kernel_nf, C, O, K, A, W);                                          \
+    } while (0)
+#define PGX_STEP2(C, O, K, A, W)                                                                             \
+    do {                                                                                                     \
+        if (two) {                                                                                           \
+            hipLaunchKernelGGL((step_kernel_o2_nf<C, O, K, A, W>), grid, block, 0, st, m, e, s, action, o, nf); \
+            if (name) *name = PGX_KNAME(step_kernel_o2_nf, C, O, K, A, W);                                   \
+        } else {                                                                                             \
+            PGX_STEP(C, O, K, A, W);                                                                         \
+        }                                                                                                    \
+    } while (0)
+#else
+#define PGX_FN(f) f
 #define PGX_STEP(C, O, K, A, W)                                                                   \
     do {                                                                                          \
         hipLaunchKernelGGL((step_kernel<C, O, K, A, W>), grid, block, 0, st, m, e, s, action, o); \
@@ -5263,6 +5399,7 @@ __global__ __launch_bounds__(SORT_SEG_MAX) void env_sort_segment_kernel(PgxDevSt
             PGX_STEP(C, O, K, A, W);                                                                  \
         }                                                                                             \
     } while (0)
+#endif
 #if PGX_TU != 3 && PGX_TU != 4
 /* The heavy-first env order of the per-pair manifold launches (wide layout), from 256 waves (1024
  * envs) on.  Rounds 4-5 sorted only beyond the waves the chip holds at once (longest-first
@@ -5302,8 +5439,8 @@ static PgxDevEnv sort_envs(const PgxDevEnv& e, const PgxDevState& s, hipStream_t
 }
 #endif
 #if PGX_TU == 4 || PGX_TU == 0
-int pgx_launch_step_ao(const PgxDevModel* m, const PgxDevEnv& e, const PgxDevState& s, const float* action,
-                       const PgxDevOut& o, void* stream, const char** name, bool two, bool wide) {
+int PGX_FN(pgx_launch_step_ao)(const PgxDevModel* m, const PgxDevEnv& e, const PgxDevState& s, const float* action,
+                               const PgxDevOut& o, void* stream, const char** name, bool two, bool wide, uint8_t* nf) {
     hipStream_t st = (hipStream_t)stream;
     const int per_block = wide ? EPW : 64;
     dim3 block(64), grid((e.n_envs + per_block - 1) / per_block);
@@ -5314,8 +5451,8 @@ int pgx_launch_step_ao(const PgxDevModel* m, const PgxDevEnv& e, const PgxDevSta
 }
 #endif
 #if PGX_TU != 2 && PGX_TU != 3 && PGX_TU != 4
-int pgx_launch_step_arm(const PgxDevModel* m, const PgxDevEnv& e, const PgxDevState& s, const float* action,
-                        const PgxDevOut& o, void* stream, const char** name) {
+int PGX_FN(pgx_launch_step_arm)(const PgxDevModel* m, const PgxDevEnv& e, const PgxDevState& s, const float* action,
+                                const PgxDevOut& o, void* stream, const char** name, uint8_t* nf) {
     hipStream_t st = (hipStream_t)stream;
     const int wide = e.lanes_per_env == GW;
     const int per_block = wide ? EPW : 64;
@@ -5346,9 +5483,18 @@ int pgx_launch_step_arm(const PgxDevModel* m, const PgxDevEnv& e, const PgxDevSt
 }
 #endif
 #if PGX_TU != 1 && PGX_TU != 3 && PGX_TU != 4
-int pgx_launch_step(const PgxDevModel* m, const PgxDevEnv& e, const PgxDevState& s, const float* action,
-                    const PgxDevOut& o, void* stream, const char** name) {
-    if (!e.ao && !e.has_object) return pgx_launch_step_arm(m, e, s, action, o, stream, name);
+int PGX_FN(pgx_launch_step)(const PgxDevModel* m, const PgxDevEnv& e, const PgxDevState& s, const float* action,
+                             const PgxDevOut& o, void* stream, const char** name, uint8_t* nf) {
+#if !PGX_NF
+    if (e.nonfinite_guard) {   /* the guarded kernels: units of their own (PGX_NF above) */
+#if PGX_TU == 0 || defined(PGX_NO_NF)
+        return (int)hipErrorNotSupported;
+#else
+        return pgx_launch_step_nf(m, e, s, action, o, stream, name, nf);
+#endif
+    }
+#endif
+    if (!e.ao && !e.has_object) return PGX_FN(pgx_launch_step_arm)(m, e, s, action, o, stream, name, nf);
     hipStream_t st = (hipStream_t)stream;
     const int wide = e.lanes_per_env == GW;
     const int per_block = wide ? EPW : 64;
@@ -5365,7 +5511,7 @@ int pgx_launch_step(const PgxDevModel* m, const PgxDevEnv& e, const PgxDevState&
          * 32 KB of LDS per wave lets only 5 of the two-wave build's 8 waves per CU in, and at 256
          * registers it spills 676 B per lane (PickAndPlace 16384: 8.54 ms two-wave, 4.51 ms one
          * wave, profiles/r04/ab_full_waves_start.log) */
-        if (e.ao) return pgx_launch_step_ao(m, e, s, action, o, stream, name, two, true);
+        if (e.ao) return PGX_FN(pgx_launch_step_ao)(m, e, s, action, o, stream, name, two, true, nf);
         switch (variant) {
             case 3: PGX_STEP(0, 1, 1, 0, 2); break;
             case 7: PGX_STEP(1, 1, 1, 0, 2); break;
@@ -5373,7 +5519,7 @@ int pgx_launch_step(const PgxDevModel* m, const PgxDevEnv& e, const PgxDevState&
         }
         return (int)hipGetLastError();
     }
-    if (e.ao) return pgx_launch_step_ao(m, e, s, action, o, stream, name, two, wide);
+    if (e.ao) return PGX_FN(pgx_launch_step_ao)(m, e, s, action, o, stream, name, two, wide, nf);
     switch (variant * 2 + wide) {
         case 6: PGX_STEP(0, 1, 1, 0, 0); break;
         case 7: PGX_STEP2(0, 1, 1, 0, 1); break;
@@ -5384,6 +5530,7 @@ int pgx_launch_step(const PgxDevModel* m, const PgxDevEnv& e, const PgxDevState&
     return (int)hipGetLastError();
 }
 
+#if !PGX_NF
 int pgx_launch_reset(const PgxDevModel* m, const PgxDevEnv& e, const PgxDevState& s, const uint8_t* mask,
                      const double* inject_goal, const double* inject_obj, const PgxDevOut& o, void* stream) {
     dim3 block(64), grid((e.n_envs + 63) / 64);
@@ -5419,7 +5566,19 @@ int pgx_launch_set_word(int32_t* p, int32_t v, void* stream) {
     hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, p, v);
     return (int)hipGetLastError();
 }
+/* pgx_step_out.nonfinite of a handle without the guard: all zero (a kernel node, as above) */
+__global__ __launch_bounds__(256) void zero_flags_kernel(uint8_t* p, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = 0;
+}
+int pgx_launch_zero_flags(uint8_t* p, int n, void* stream) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(zero_flags_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, n);
+    return (int)hipGetLastError();
+}
+#endif  /* !PGX_NF */
 #endif  /* PGX_TU 0 or 2 */
 #undef PGX_STEP
 #undef PGX_STEP2
+#undef PGX_FN
 #undef PGX_KNAME

@@ -252,10 +252,20 @@ class PandaVecEnv(_VecEnvBase):
                  n_substeps: int = 20, model_name: str = "panda_custom0", contacts: bool = True,
                  lanes_per_env: int = 0, full_manifold: Optional[bool] = None,
                  sim_params: Optional[Dict[str, Any]] = None, lib_path: Optional[str] = None,
-                 reset_rng: str = "philox"):
+                 reset_rng: str = "philox", nonfinite: str = "off"):
         """``sim_params``: pgx_sim_params fields to override (the default library runs only the
         compiled parameters and refuses others; ``lib_path`` = libpgx_rtmodel.so reads them from
-        the handle)."""
+        the handle).
+
+        ``nonfinite``: the per-env non-finite guard (pgx_config.nonfinite_guard).
+        ``"off"`` (default): none -- an env whose state turns NaN / inf keeps writing NaN
+        observations until its time limit.  ``"reset"``: the step kernel catches such an env in the
+        step its state turns non-finite, reports that step as reward 0 / truncated (``nonfinite()``,
+        ``infos[i]["nonfinite"]``), and resets it like a time-limit truncation; every other env is
+        bit for bit what it is without the guard.  ``"raise"``: the same on the device, and the host
+        paths that look (``step_wait``, ``raise_device_errors``) raise PgxError naming the envs."""
+        if nonfinite not in NONFINITE_MODES:
+            raise ValueError(f"nonfinite must be one of {NONFINITE_MODES}, got {nonfinite!r}")
         if torch is None:
             raise PgxError("PandaVecEnv needs torch for device buffers")
         self.lib = load(lib_path)
@@ -298,7 +308,10 @@ class PandaVecEnv(_VecEnvBase):
         # auto_reset=False: a finished env keeps its terminal state until reset (one gymnasium env)
         self._cfg.no_auto_reset = 0 if auto_reset else 1
         self.auto_reset = bool(auto_reset)
-        self.obs_dim = self.lib.pgx_obs_dim(C.byref(self._cfg))
+        self.nonfinite_mode = nonfinite
+        self._cfg.nonfinite_guard = 0 if nonfinite == "off" else 1
+        self.nonfinite_resets = 0   # caught env-steps the host paths have seen (step_wait, raise_device_errors)
+        self.obs_dim =self.lib.pgx_obs_dim(C.byref(self._cfg))
         self.action_dim = self.lib.pgx_action_dim(C.byref(self._cfg))
         h = C.c_void_p()
         torch.cuda.set_device(self.device)
@@ -313,7 +326,9 @@ class PandaVecEnv(_VecEnvBase):
                ("terminal_obs", (n, od)), ("terminal_ag", (n, 3)), ("terminal_dg", (n, 3))]
         # Task.is_truncated (task_trunc, ReachAO is_collided): written by the kernel; zero for the others
         u8 = ["success", "terminated", "truncated", "task_trunc"]
-        nf = sum(int(np.prod(shape)) for _, shape in f32)
+        if nonfinite != "off":   # the guard's per-env flag: a fifth row (without the guard, the layout as ever)
+            u8.append("nonfinite_t")
+        nf =sum(int(np.prod(shape)) for _, shape in f32)
         self._outbuf = torch.zeros(4 * nf + len(u8) * n, dtype=torch.uint8, **kw)
         self._out_f32 = self._outbuf[:4 * nf].view(torch.float32)
         self._out_u8 = self._outbuf[4 * nf:].view(len(u8), n)
@@ -329,7 +344,10 @@ class PandaVecEnv(_VecEnvBase):
                                    self.reward.data_ptr(), self.success.data_ptr(), self.terminated.data_ptr(),
                                    self.truncated.data_ptr(), self.terminal_obs.data_ptr(), self.terminal_ag.data_ptr(),
                                    self.terminal_dg.data_ptr(),
-                                   self.task_trunc.data_ptr() if self.spec.task == abi.TASK_REACH_AO else None)
+                                   self.task_trunc.data_ptr() if self.spec.task == abi.TASK_REACH_AO else None,
+                                   self.nonfinite_t.data_ptr() if nonfinite != "off" else None)
+        if nonfinite == "off":   # nothing writes it: all False
+            self.nonfinite_t = torch.zeros(n, dtype=torch.uint8, **kw)
         self.observation_space, self.action_space = make_spaces(od, self.action_dim)
         self.distance_threshold = self.spec.distance_threshold
         if self.spec.task == abi.TASK_REACH_AO:
@@ -403,16 +421,33 @@ class PandaVecEnv(_VecEnvBase):
         self._check(self.lib.pgx_get_state(self._h, C.byref(v)), "pgx_get_state")
         return int(v.robot_points)
 
-    def raise_device_errors(self, errors: Optional[int] = None) -> None:
+    def raise_device_errors(self, errors: Optional[int] = None, caught: Optional[np.ndarray] = None) -> None:
         """Raise what the kernels flagged (pgx_state_view.errors) and clear it.  The device path
         (step_tensors / reset_tensors) never synchronises to look; the SB3 path (reset,
         step_wait) looks at every call.  PGX_ERR_AO_OBSTACLE: ReachAO.set_coll_free_obs raises
-        StopIteration after 10000 rejected obstacle draws (reach_ao.py:1143-1145)."""
+        StopIteration after 10000 rejected obstacle draws (reach_ao.py:1143-1145).
+        PGX_ERR_NONFINITE (the non-finite guard, ``nonfinite``): counted into ``nonfinite_resets``
+        and cleared in mode ``"reset"``, raised in mode ``"raise"``; ``caught``: the env ids of the
+        last step's mask where the caller has them on the host already (else read here)."""
         err = self.state()["errors"]
         if errors is None:
             errors = int(err.item())
         if errors:
             err.zero_()
+            if errors & abi.ERR_NONFINITE:
+                # the non-finite guard (``nonfinite``): "reset" counts the envs of the last step's mask
+                # and goes on, "raise" names them
+                if caught is None:
+                    caught = np.flatnonzero(self.nonfinite())
+                self.nonfinite_resets += int(len(caught))
+                if self.nonfinite_mode == "raise":
+                    ids = ", ".join(map(str, caught.tolist()[:16])) + (", ..." if len(caught) > 16 else "")
+                    raise PgxError("PGX_ERR_NONFINITE: the non-finite guard caught NaN / inf state in "
+                                   + (f"env(s) {ids} in the last step" if len(caught) else "an earlier step")
+                                   + f" (device error flags 0x{errors:x})")
+                errors &= ~abi.ERR_NONFINITE
+                if not errors:
+                    return
             if errors & abi.ERR_AO_OBSTACLE:
                 raise PgxError("Couldn't find collision free obstacle! (device reset of a ReachAO env gave up "
                                "after 10000 obstacle draws; reach_ao.py:1143-1145 raises StopIteration)")
@@ -570,7 +605,8 @@ class PandaVecEnv(_VecEnvBase):
                 k = int(np.prod(shape))
                 self._hs[name] = hf[o:o + k].view(shape)
                 o += k
-            self._hs["flags"] = self._hs["packed"][4 * nf:].view(4, n)   # success, terminated, truncated, task
+            # success, terminated, truncated, task (+ the non-finite guard's flag where it is on)
+            self._hs["flags"] = self._hs["packed"][4 * nf:].view(self._out_u8.shape[0], n)
         return self._hs
 
     def step_async(self, actions) -> None:
@@ -600,8 +636,10 @@ class PandaVecEnv(_VecEnvBase):
         # in C from the common template, the few envs whose flags differ patched after the sync
         infos: List[Dict[str, Any]] = list(map(dict.copy, [_INFO_TEMPLATES[0]] * self.num_envs))
         stream.synchronize()
+        guard = self.nonfinite_mode != "off"
         if hs["errors"].item():
-            self.raise_device_errors(int(hs["errors"].item()))
+            self.raise_device_errors(int(hs["errors"].item()),
+                                     caught=np.flatnonzero(hs["flags"].numpy()[4]) if guard else None)
         # copies: the pinned mirrors are overwritten by the next step
         o = {k: hs[k].numpy().copy() for k in ("observation", "achieved_goal", "desired_goal")}
         r = hs["reward"].numpy().copy()
@@ -618,6 +656,11 @@ class PandaVecEnv(_VecEnvBase):
                 infos[i]["terminal_observation"] = {"observation": tobs[i].copy(), "achieved_goal": tag[i].copy(),
                                                     "desired_goal": tdg[i].copy()}
                 infos[i]["TimeLimit.truncated"] = bool(tr[i] and not te[i])
+        if guard:   # envs the guard caught: truncated, their terminal rows the reset's (finite)
+            for i in np.flatnonzero(fl[4]).tolist():
+                infos[i]["nonfinite"] = True
+                if not self.auto_reset:   # (no reset, no terminal rows: the env keeps its state for the host)
+                    infos[i].pop("terminal_observation", None)
         return o, r, d, infos
 
     def step(self, actions):
@@ -629,6 +672,11 @@ class PandaVecEnv(_VecEnvBase):
         (reach.py:53-54); ReachAO's is_collided (reach_ao.py:1263-1264), the kernel's own
         collision flag (pgx_step_out.task_truncated), whatever collision_reward is."""
         return self.task_trunc.cpu().numpy() != 0
+
+    def nonfinite(self) -> np.ndarray:
+        """Envs the non-finite guard caught in the last step (pgx_step_out.nonfinite; ``nonfinite_t``
+        is the device tensor): all False without the guard (``nonfinite="off"``)."""
+        return self.nonfinite_t.cpu().numpy() != 0
 
     def _numpy_obs(self) -> Dict[str, np.ndarray]:
         return {k: v.cpu().numpy().copy() for k, v in self._obs_dict().items()}
@@ -688,6 +736,7 @@ class PandaVecEnv(_VecEnvBase):
         self._check(self.lib.pgx_release(self._h, int(state_id)), "pgx_release")
 
 
+NONFINITE_MODES = ("off", "reset", "raise")
 _INFO_TEMPLATES = [{"is_success": s, "is_truncated": c} for c in (False, True) for s in (False, True)]
 
 
@@ -829,13 +878,17 @@ class PandaEnv(_EnvBase):
     render_mode = None
 
     def __init__(self, env_id: str = "PandaReach-v3", device: Any = "cuda:0", max_episode_steps: Optional[int] = None,
-                 seed: int = 0, reset_rng: str = "philox"):
-        """``reset_rng="pcg64"``: reset(seed) reseeds the env's device PCG64 stream and draws the
+                 seed: int = 0, reset_rng: str = "philox", nonfinite: str = "off"):
+        """``nonfinite``: PandaVecEnv's non-finite guard for the one env: ``"raise"`` raises PgxError from
+        ``step``, ``"reset"`` returns ``truncated=True`` with ``info["nonfinite"] = True`` (the env keeps
+        its state: the caller resets).
+
+        ``reset_rng="pcg64"``: reset(seed) reseeds the env's device PCG64 stream and draws the
         reference's goal / object for that seed (core.py:302); a later reset() without a seed
         continues the stream -- a reproducible stand-in for the fresh OS entropy the reference
         draws there, not a reference value (PandaVecEnv)."""
         self._vec = PandaVecEnv(env_id, num_envs=1, device=device, seed=seed, auto_reset=False,
-                                max_episode_steps=max_episode_steps, reset_rng=reset_rng)
+                                max_episode_steps=max_episode_steps, reset_rng=reset_rng, nonfinite=nonfinite)
         # (gymnasium.make replaces env.spec with its registry EnvSpec: the env reads self._vec.spec)
         self.spec = self._vec.spec
         self.observation_space = self._vec.observation_space
@@ -864,6 +917,10 @@ class PandaEnv(_EnvBase):
         # the kernel's truncated flag = Task.is_truncated (ReachAO collision) or the TimeLimit
         # (gymnasium TimeLimit.step ORs them); info carries the task's own flag (core.py:363-365)
         info = {"is_success": bool(succ[0].item()), "is_truncated": bool(self._vec.task_truncated()[0])}
+        if self._vec.nonfinite_mode != "off":
+            self._vec.raise_device_errors()   # "raise": raises here; "reset": counts and clears the bit
+            if self._vec.nonfinite()[0]:
+                info["nonfinite"] = True
         return o, r, bool(term[0].item()), bool(trunc[0].item()), info
 
     def compute_reward(self, achieved_goal, desired_goal, info=None):
