@@ -328,7 +328,14 @@ typedef struct pgx_state_view {
     int32_t* env_order;    /* [N] the env order of the last step launch that sorted its envs heavy-first
                               (per-pair manifold kernels; position -> env id), the identity before
                               the first such launch, NULL for handles without the per-pair budget;
-                              not state (the next sorted launch rewrites it) */
+                              not state (the next sorted launch rewrites it).  From a handle's
+                              second step on, the step kernel derives the order itself, from one
+                              key byte per env that the previous step's epilogue wrote (segments
+                              of <= 1024 envs; PGX_SORT_FUSED=0: the sort kernel at every launch).
+                              pgx_reset, pgx_restore_state and pgx_restore make the next step sort
+                              from the state as it stands; pgx_get_state does not, so a caller who
+                              writes `contacts` through this view steps once in an order one step
+                              stale -- any order gives every env the same bits */
     float* manifolds;      /* [1 + manifold_pool * PGX_MANIFOLD_POINT][N] the persistent manifold pool
                               (PGX_MANIFOLD_POOL above), NULL without one */
     int32_t manifold_pool; /* its capacity in points (0: none) */

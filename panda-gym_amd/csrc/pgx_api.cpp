@@ -82,6 +82,15 @@ struct pgx_env {
     int man_pool = 0;       /* persistent manifold pool capacity (0: none) */
     /* the step kernel the last pgx_step launched (pgx_step_kernel) */
     const char* step_kernel = nullptr;
+    /* the sort keys of the heavy-first order (PgxDevEnv.keys_in / keys_out): the two arrays, the one
+     * the next launch writes, and whether the other holds the keys of the state as it stands -- true
+     * after a pgx_step, false after anything else that changes the state (create, reset, restore):
+     * the next step then sorts with env_sort_segment_kernel as before.  sort_fused: PGX_SORT_FUSED=0
+     * (A/B and test hook) sorts with the kernel at every launch */
+    uint8_t* key_buf[2] = {nullptr, nullptr};
+    int key_write = 0;
+    bool keys_fresh = false;
+    bool sort_fused = true;
 };
 
 extern "C" {
@@ -465,6 +474,9 @@ int pgx_create(const pgx_config* cfg, int device, pgx_handle* out) {
     e.sort_segs = 0;   /* PGX_SORT_SEGS=1: one global heavy-first order (A/B hook; default: per-XCD segments) */
     if (const char* sg = std::getenv("PGX_SORT_SEGS")) e.sort_segs = std::atoi(sg) == 1 ? 1 : 0;
     e.perm_segs = 1;
+    e.keys_in = nullptr;
+    e.keys_out = nullptr;
+    if (const char* sf = std::getenv("PGX_SORT_FUSED")) h->sort_fused = std::atoi(sf) != 0;
     e.task = cfg->task;
     e.control = cfg->control;
     e.reward = cfg->reward;
@@ -554,7 +566,10 @@ int pgx_create(const pgx_config* cfg, int device, pgx_handle* out) {
            off_man = align(off_ao + (e.ao ? 4 * PGX_AO_OBSTACLES * N * 4 : 0)),
            off_el = align(off_man + man_rows * N * 4), off_ep = align(off_el + N * 4),
            off_err = align(off_ep + N * 4), off_perm = align(off_err + 4),
-           total = align(off_perm + (e.full_manifold ? N * 4 + (N + 3) / 4 * 4 + (N / 256 + 1) * 13 * 4 : 0));
+           /* the sort kernels' arrays, then the two key arrays of the fused order (16 B loads) */
+           off_keys = off_perm + ((e.full_manifold ? N * 4 + (N + 3) / 4 * 4 + (N / 256 + 1) * 13 * 4 : 0) + 15) / 16 * 16,
+           key_bytes = (N + 15) / 16 * 16,
+           total = align(off_keys + (e.full_manifold ? 2 * key_bytes : 0));
     rc = hip_check(hipMalloc(&h->blob, total), "hipMalloc(state)");
     if (rc) { delete h; return rc; }
     h->blob_bytes = total;
@@ -570,7 +585,11 @@ int pgx_create(const pgx_config* cfg, int device, pgx_handle* out) {
     h->ds.elapsed = (int32_t*)(b + off_el);
     h->ds.episode = (uint32_t*)(b + off_ep);
     h->ds.errors = (uint32_t*)(b + off_err);
-    if (e.full_manifold) e.perm_buf = (int32_t*)(b + off_perm);   /* heavy-first env order (not state) */
+    if (e.full_manifold) {   /* heavy-first env order (not state) */
+        e.perm_buf = (int32_t*)(b + off_perm);
+        h->key_buf[0] = (uint8_t*)(b + off_keys);
+        h->key_buf[1] = (uint8_t*)(b + off_keys + key_bytes);
+    }
     h->dm_dev = (PgxDevModel*)b;
     /* the PCG64 reset streams and their mode word: not part of the saved state (restoreState leaves
      * np_random alone), so outside the blob */
@@ -663,6 +682,7 @@ int pgx_reset(pgx_handle h, const uint8_t* env_mask, const double* inject_goal, 
     if (!h) return fail(PGX_E_INVALID, "null handle");
     if (inject_object && !h->de.has_object && !h->de.ao)
         return fail(PGX_E_INVALID, "object injection needs an object task (or ReachAO obstacles)");
+    h->keys_fresh = false;
     return hip_check((hipError_t)pgx_launch_reset(h->dm_dev, h->de, h->ds, env_mask, inject_goal, inject_object,
                                                   to_dev_out(out), stream),
                      "reset launch");
@@ -674,9 +694,18 @@ int pgx_step(pgx_handle h, const float* action, pgx_step_out* out, void* stream)
         const int rc = hip_check((hipError_t)pgx_launch_zero_flags(out->nonfinite, h->de.n_envs, stream), "flags launch");
         if (rc) return rc;
     }
-    return hip_check((hipError_t)pgx_launch_step(h->dm_dev, h->de, h->ds, action, to_dev_out(out), stream,
-                                                 &h->step_kernel, out ? out->nonfinite : nullptr),
-                     "step launch");
+    if (h->de.perm_buf) {   /* this launch's key arrays: it reads the one the last step wrote, if that still holds */
+        h->de.keys_out = h->key_buf[h->key_write];
+        h->de.keys_in = (h->sort_fused && h->keys_fresh) ? h->key_buf[h->key_write ^ 1] : nullptr;
+    }
+    const int rc = hip_check((hipError_t)pgx_launch_step(h->dm_dev, h->de, h->ds, action, to_dev_out(out), stream,
+                                                         &h->step_kernel, out ? out->nonfinite : nullptr),
+                             "step launch");
+    if (h->de.perm_buf) {
+        h->key_write ^= 1;
+        h->keys_fresh = rc == PGX_OK;
+    }
+    return rc;
 }
 
 const char* pgx_step_kernel(pgx_handle h) { return h ? h->step_kernel : nullptr; }
@@ -709,6 +738,7 @@ int pgx_save_state(pgx_handle h, void* dst, void* stream) {
 
 int pgx_restore_state(pgx_handle h, const void* src, void* stream) {
     if (!h || !src) return fail(PGX_E_INVALID, "null argument");
+    h->keys_fresh = false;
     return hip_check(hipMemcpyAsync(h->blob, src, h->blob_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream),
                      "restore_state copy");
 }
@@ -743,6 +773,7 @@ static bool snap_valid(pgx_handle h, int32_t id) {
 int pgx_restore(pgx_handle h, int32_t state_id, void* stream) {
     if (!h) return fail(PGX_E_INVALID, "null handle");
     if (!snap_valid(h, state_id)) return fail(PGX_E_INVALID, "Couldn't restore state %d: no such saved state", state_id);
+    h->keys_fresh = false;
     return hip_check(hipMemcpyAsync(h->blob, h->snaps[state_id], h->blob_bytes, hipMemcpyDeviceToDevice,
                                     (hipStream_t)stream),
                      "restore copy");

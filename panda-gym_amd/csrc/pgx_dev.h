@@ -93,7 +93,8 @@ struct PgxDevEnv {
                                       device memory and switched on the caller's stream, so a step loop
                                       captured in a HIP graph draws in the mode of replay time */
     /* heavy-first env order of the per-pair manifold kernels (pgx_launch_step): perm_buf device
-     * buffer (permutation [N] i32, keys [N] u8 padded to 4 B, per-block bin counts [N/256 + 1][13]); sort_mode (PGX_SORT_ENVS) 0 auto (more waves than fit at once), 1 always, -1 never;
+     * buffer (permutation [N] i32, keys [N] u8 padded to 4 B, per-block bin counts [N/256 + 1][13], then
+     * the two key arrays of keys_in / keys_out below, [N] u8 padded to 16 B each); sort_mode (PGX_SORT_ENVS) 0 auto (more waves than fit at once), 1 always, -1 never;
      * perm: the order a launch uses (nullptr: identity), set by the launcher */
     int32_t* perm_buf;
     int32_t sort_mode;
@@ -102,6 +103,13 @@ struct PgxDevEnv {
     const int32_t* perm;
     int32_t perm_segs;             /* the launch's segments: 8 = perm is heavy-first within each XCD's env range */
     int32_t nonfinite_guard;       /* pgx_config.nonfinite_guard: the launchers pick the step kernels' _nf builds */
+    /* the sort keys, a byte per env, two arrays after perm_buf's (not state): every per-pair manifold
+     * step kernel's epilogue writes keys_out, and a launch whose keys_in is set (pgx_step: the last
+     * call that changed the handle's state was a step; segments of <= 1024 envs, the launcher)
+     * derives its heavy-first order from them in its prologue instead of reading a sorted perm.
+     * pgx_step swaps the two at every launch: no wave writes the array another wave still reads */
+    const uint8_t* keys_in;
+    uint8_t* keys_out;
 };
 
 struct PgxDevState {

@@ -4639,6 +4639,133 @@ __device__ __forceinline__ int xcd_block() {
     return (b % 8) * (nb / 8) + b / 8;
 }
 
+/* the block whose env slots this wave steps: dispatch order under one global heavy-first order,
+ * else the XCD's contiguous range (the prologue and ReachAO's epilogue both ask) */
+__device__ __forceinline__ int env_block(const PgxDevEnv& e) {
+    return (e.perm && e.perm_segs == 1) ? (int)blockIdx.x : xcd_block();
+}
+
+/* The heavy-first env order without a sort launch: the previous step's
+ * epilogue left one key byte per env (the robot slots its cache row holds, env_sort_segment_kernel's
+ * formula), and each wave of a per-pair manifold kernel derives the envs of its own EPW slots from
+ * the keys of its segment (<= 1024 envs: the whole batch, or its XCD's range) -- the stable
+ * counting sort of the sort kernels, most points first, inverted for EPW consecutive ranks only.
+ *
+ * Lane l holds the keys of the segment's envs [16 l, 16 l + 16), a byte each (bytes past the segment
+ * 0: the lightest bin's last places, which no slot below N asks for).  1. The bin of the wave's
+ * first rank r0, by bisection over the bins 0..TOP (the kernel's robot budget): per probe the
+ * lanes' counts of keys >= mid by byte compares and their sum over the wave (a DPP prefix sum, its
+ * last lane read into an SGPR) -- log2 of the bins, whichever of them the batch fills (the headline
+ * holds 0 to 2 points per env: a walk down from bin 12 would pass ten empty bins first).  2. From
+ * that bin down, until the base passes the wave's last rank (one bin, or the few the wave's ranks
+ * straddle): the lanes' counts of keys == k, their inclusive prefix sum, the bin's total; rank
+ * r = base + p belongs to the lane whose prefix interval holds p (a ballot) and there to that
+ * lane's (p - exclusive prefix)-th key of the bin.  3. The pick inside the lane runs once, for all
+ * rows at a time: lane 16 t + b looks at byte b of the lane row t found.
+ *
+ * Wave-wide (ballots, DPP, readlane, bpermute): called by all 64 lanes of the block, before any of
+ * them returns.  The result is clamped into the segment, whatever the keys hold.  The host model
+ * of these steps, lane for lane: pgx_order_model.cpp (tests/test_env_order_model.py). */
+constexpr int SORT_BINS = PGX_ROBOT_POINTS + 1;
+constexpr int SORT_SEG_MAX = 1024;
+constexpr int ORDER_KPL = SORT_SEG_MAX / 64;   /* keys per lane */
+static_assert(ORDER_KPL == GW && EPW * GW == 64, "the pick inside the lane: one lane of the env's row per key");
+template <int CTRL, int ROWS>
+__device__ __forceinline__ int dpp_add0(int x) {   /* x + the DPP source's x (0 where there is none) */
+    return x + __builtin_amdgcn_update_dpp(0, x, CTRL, ROWS, 0xF, false);
+}
+__device__ __forceinline__ int wave_prefix_sum(int x) {   /* inclusive, over the 64 lanes */
+    x = dpp_add0<0x111, 0xF>(x);   /* row_shr:1 */
+    x = dpp_add0<0x112, 0xF>(x);   /* row_shr:2 */
+    x = dpp_add0<0x114, 0xF>(x);   /* row_shr:4 */
+    x = dpp_add0<0x118, 0xF>(x);   /* row_shr:8 */
+    x = dpp_add0<0x142, 0xA>(x);   /* row_bcast:15 into rows 1, 3 */
+    x = dpp_add0<0x143, 0xC>(x);   /* row_bcast:31 into rows 2, 3 */
+    return x;
+}
+template <int TOP>
+__device__ __forceinline__ int order_env(const uint8_t* __restrict__ keys, int N, int segs, int ln) {
+    const int lane = (int)threadIdx.x;
+    /* segs == 8: N is a multiple of 8 x 256 and block b steps XCD b % 8's range (xcd_block) */
+    const int S = segs == 1 ? N : N >> 3;
+    const int base = segs == 1 ? 0 : (int)(blockIdx.x & 7u) * S;
+    const int r0 = (segs == 1 ? (int)blockIdx.x : (int)(blockIdx.x >> 3)) * EPW;   /* the wave's first rank */
+    const int nv = S - ORDER_KPL * lane;   /* this lane's keys inside the segment */
+    uint32_t kw[4] = {0u, 0u, 0u, 0u};
+    if (nv > 0) {
+        const uint4 v = *reinterpret_cast<const uint4*>(keys + base + ORDER_KPL * lane);
+        kw[0] = v.x; kw[1] = v.y; kw[2] = v.z; kw[3] = v.w;
+    }
+    /* every byte < 0x80, whatever was read, and 0 past the segment (a ragged one ends inside a lane) */
+    if (S & (ORDER_KPL - 1)) {
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            const int nd = nv - 4 * d;
+            kw[d] &= nd <= 0 ? 0u : 0x7f7f7f7fu >> (32 - 8 * min(nd, 4));
+        }
+    } else {
+#pragma unroll
+        for (int d = 0; d < 4; d++) kw[d] &= 0x7f7f7f7fu;
+    }
+    /* 1. lo = the heaviest bin with more than r0 envs in it and above, B = the envs above it (uniform) */
+    int lo = 0, hi = TOP, B = 0;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        const uint32_t up = 0x01010101u * (uint32_t)(0x80 - mid);   /* byte + 0x80 - mid sets bit 7 exactly when byte >= mid */
+        int c = 0;
+#pragma unroll
+        for (int d = 0; d < 4; d++) c += __popc((kw[d] + up) & 0x80808080u);
+        const int g = __builtin_amdgcn_readlane(wave_prefix_sum(c), 63);
+        if (g > r0) {
+            lo = mid;
+        } else {
+            hi = mid - 1;
+            B = g;
+        }
+    }
+    /* 2. */
+    int lsel = 0, jsel = 0, ksel = 0xff;   /* this row's rank: the lane, the place among its keys of the bin, the bin */
+    for (int k = lo; k >= 0; k--) {
+        const uint32_t kk = 0x01010101u * (uint32_t)k;
+        int nz = 0;   /* bytes != k: keys are < 0x80, so byte + 0x7f carries into bit 7 exactly when it is not 0 */
+#pragma unroll
+        for (int d = 0; d < 4; d++) nz += __popc(((kw[d] ^ kk) + 0x7f7f7f7fu) & 0x80808080u);
+        const int c = ORDER_KPL - nz;
+        const int x = wave_prefix_sum(c);
+        const int T = __builtin_amdgcn_readlane(x, 63);
+        const int p0 = r0 - B;   /* the wave's first rank, counted inside this bin */
+        if (p0 < T && p0 + EPW > 0) {
+            const int E = x - c;
+#pragma unroll
+            for (int t = 0; t < EPW; t++) {
+                const int p = p0 + t;
+                if (p >= 0 && p < T) {   /* (uniform) */
+                    /* the lanes before it: those whose inclusive sum has not passed p (p < T: not all) */
+                    const int lt = min((int)__popcll(__ballot(x <= p)), 63);
+                    const int j = p - __builtin_amdgcn_readlane(E, lt);
+                    if (ln == t) { lsel = lt; jsel = j; ksel = k; }
+                }
+            }
+        }
+        B += T;
+        if (B >= r0 + EPW) break;
+    }
+    /* 3. lane 16 t + b: byte b of lane lsel's keys */
+    const int b = lane & (ORDER_KPL - 1);
+    uint32_t w = (uint32_t)__shfl((int)kw[0], lsel);
+    const uint32_t w1 = (uint32_t)__shfl((int)kw[1], lsel), w2 = (uint32_t)__shfl((int)kw[2], lsel),
+                   w3 = (uint32_t)__shfl((int)kw[3], lsel);
+    w = (b >> 2) == 1 ? w1 : w;
+    w = (b >> 2) == 2 ? w2 : w;
+    w = (b >> 2) == 3 ? w3 : w;
+    const bool match = (int)((w >> (8 * (b & 3))) & 0xffu) == ksel;
+    const uint32_t gm = (uint32_t)(__ballot(match) >> (ORDER_KPL * ln)) & 0xffffu;
+    const bool hit = match && __popc(gm & ((1u << b) - 1u)) == jsel;
+    const uint32_t gh = (uint32_t)(__ballot(hit) >> (ORDER_KPL * ln)) & 0xffffu;
+    const int i = base + ORDER_KPL * lsel + (int)__builtin_ctz(gh | 0x10000u);
+    return min(max(i, base), base + S - 1);
+}
+
 /* WIDE = 0: one env per lane (64 per wave); WIDE = 1: 16 lanes per env (4 per wave,
  * substep_g), the redundant lanes compute the same values and only the lead lane stores. */
 /* GUARD = 1 (pgx_config.nonfinite_guard, the step_kernel_nf builds): the non-finite guard, on entry
@@ -4659,9 +4786,25 @@ __device__ __forceinline__ void step_body(const PgxDevModel* __restrict__ mdev, 
     const int N = e.n_envs;
     /* heavy-first order (e.perm, pgx_launch_step): dispatch order = block order, so the blocks are
      * not dealt out per XCD there; an env's result does not depend on its wave mates */
-    const int slot = ((e.perm && e.perm_segs == 1) ? (int)blockIdx.x : xcd_block()) * (WIDE ? EPW : 64) + ln;
+    const int slot = env_block(e) * (WIDE ? EPW : 64) + ln;
+    /* the order from the previous step's keys (e.keys_in, pgx_step: order_env above), by the whole
+     * wave before the lanes of a ragged batch's empty slots leave */
+    bool keyed = false;
+    int ikey = 0;
+    if constexpr (WIDE == 2) {
+        keyed = e.keys_in != nullptr;
+        if (keyed) ikey = order_env<LT::RB>(e.keys_in, N, e.perm_segs, ln);
+    }
     if (slot >= N) return;
-    const int i = e.perm ? e.perm[slot] : slot;
+    int i;
+    if (keyed) {
+        /* the launch's order on record (pgx_state_view.env_order), and what ReachAO's epilogue reads
+         * again: every lane of the row stores, so each reads back its own store */
+        i = ikey;
+        e.perm_buf[slot] = i;
+    } else {
+        i = e.perm ? e.perm[slot] : slot;
+    }
 #ifdef PGX_CHECK_PERM
     /* debug builds (make dbg DBG=-DPGX_CHECK_PERM): the heavy-first permutation is a bijection of
      * [0, N) (env_sort_scatter_kernel); an entry outside it would index every state row out of range */
@@ -4869,7 +5012,7 @@ __device__ __forceinline__ void step_body(const PgxDevModel* __restrict__ mdev, 
     if constexpr (AO) {   /* (ReachAO only: the headline kernel measured +0.9 % with it, profiles/r06/ab_v19.log) */
         int lnx = ln;
         asm volatile("" : "+v"(lnx));
-        const int sl = ((e.perm && e.perm_segs == 1) ? (int)blockIdx.x : xcd_block()) * (WIDE ? EPW : 64) + lnx;
+        const int sl = env_block(e) * (WIDE ? EPW : 64) + lnx;
         ie = e.perm ? __hip_atomic_load(&e.perm[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : sl;
     }
     double goal[3];   /* read after the substep loop: not live across it */
@@ -5058,6 +5201,17 @@ __device__ __forceinline__ void step_body(const PgxDevModel* __restrict__ mdev, 
 #pragma unroll
         for (int k = 0; k < CACHE_K; k++) s.contacts[k * N + ie] = L->cache[k][ln];
     }
+    /* the next launch's sort key of the row just stored (after the auto-reset cleared it):
+     * env_sort_segment_kernel's formula, into the key array no wave of this launch reads */
+    if constexpr (WIDE == 2 && CONT) {
+        if (e.keys_out) {
+            int key = 0;
+#pragma unroll
+            for (int r = 0; r < LT::RB; r++) key += L->cache[CACHE1 + 2 * r][ln] >= 0.0f ? 1 : 0;
+            if (!e.sort_key) key = key > CG ? key - CG : 0;
+            e.keys_out[ie] = (uint8_t)key;
+        }
+    }
     s.elapsed[ie] = el;
     s.episode[ie] = episode;
 #ifdef PGX_PROF
@@ -5226,8 +5380,7 @@ __global__ __launch_bounds__(256) void compute_reward_kernel(const float* __rest
  * blocks before it, ranks its envs inside each bin by ballot, and writes the permutation.  (Order
  * does not matter for the results -- the step kernels give every env the same bits whatever its
  * wave mates, test_gpu_env_order -- but a stable sort keeps every launch reproducible.) */
-constexpr int SORT_BINS = PGX_ROBOT_POINTS + 1;
-constexpr int SORT_BLOCK = 256;
+constexpr int SORT_BLOCK = 256;   /* (SORT_BINS, SORT_SEG_MAX: above, with order_env) */
 __global__ __launch_bounds__(SORT_BLOCK) void env_sort_keys_kernel(PgxDevState s, int N, int rb, int all, uint8_t* keys,
                                                                    int32_t* blk) {
     __shared__ int32_t wc[SORT_BLOCK / 64][SORT_BINS];
@@ -5309,8 +5462,9 @@ __global__ __launch_bounds__(SORT_BLOCK) void env_sort_scatter_kernel(int N, con
 /* The same order in one launch when a segment fits one workgroup (<= 1024 envs: every batch up to
  * 8192 in eight per-XCD segments, or up to 1024 in one): block x sorts segment x -- keys, per-wave
  * ballot counts in LDS, then each env's place -- instead of the two launches above (the headline's
- * 4096 envs: one ≈ 4 µs launch for two of 4.8 + 6.3 µs). */
-constexpr int SORT_SEG_MAX = 1024;
+ * 4096 envs: one ≈ 4 µs launch for two of 4.8 + 6.3 µs).  It runs on a handle's first step and
+ * after a reset or a restore; from then on the step kernels derive the same order from the keys
+ * their epilogues wrote (order_env). */
 __global__ __launch_bounds__(SORT_SEG_MAX) void env_sort_segment_kernel(PgxDevState s, int N, int rb, int all,
                                                                         int32_t* perm) {
     __shared__ int32_t wc[SORT_SEG_MAX / 64][SORT_BINS];
@@ -5418,13 +5572,17 @@ static PgxDevEnv sort_envs(const PgxDevEnv& e, const PgxDevState& s, hipStream_t
         const int segs = (e.sort_segs != 1 && e.n_envs % (8 * SORT_BLOCK) == 0) ? 8 : 1;
         const int S = e.n_envs / segs;
         if (S <= SORT_SEG_MAX && S > 0) {
-            hipLaunchKernelGGL(env_sort_segment_kernel, dim3(segs), dim3(S), 0, st, s, e.n_envs, rb, e.sort_key,
-                               e.perm_buf);
             es.perm = e.perm_buf;
             es.perm_segs = segs;
+            /* e.keys_in (pgx_step: the previous step's keys are fresh): the step kernel derives the
+             * order itself and records it in perm_buf, nothing is launched here */
+            if (!e.keys_in)
+                hipLaunchKernelGGL(env_sort_segment_kernel, dim3(segs), dim3(S), 0, st, s, e.n_envs, rb, e.sort_key,
+                                   e.perm_buf);
             return es;
         }
     }
+    es.keys_in = nullptr;   /* larger segments: the two sort launches */
     const int nb = (e.n_envs + SORT_BLOCK - 1) / SORT_BLOCK;
     uint8_t* keys = reinterpret_cast<uint8_t*>(e.perm_buf + e.n_envs);
     int32_t* blk = e.perm_buf + e.n_envs + (e.n_envs + 3) / 4;
@@ -5462,6 +5620,7 @@ int PGX_FN(pgx_launch_step_arm)(const PgxDevModel* m, const PgxDevEnv& e, const 
         /* the heavy-first order from 1024 envs (kSortMinWaves), as the object / ReachAO launches */
         PgxDevEnv es = e;
         es.perm = nullptr;
+        es.keys_in = nullptr;   /* (the order off: the keys are still written, never read) */
         if (e.perm_buf && (e.sort_mode == 1 || (e.sort_mode == 0 && grid.x >= kSortMinWaves))) es = sort_envs(e, s, st);
         const PgxDevEnv& e = es;
         if (e.control) PGX_STEP(1, 0, 1, 0, 2);
@@ -5505,6 +5664,7 @@ int PGX_FN(pgx_launch_step)(const PgxDevModel* m, const PgxDevEnv& e, const PgxD
         const bool sort = e.perm_buf && (e.sort_mode == 1 || (e.sort_mode == 0 && grid.x >= kSortMinWaves));
         PgxDevEnv es = e;
         es.perm = nullptr;
+        es.keys_in = nullptr;   /* (the order off: the keys are still written, never read) */
         if (sort) es = sort_envs(e, s, st);
         const PgxDevEnv& e = es;
         /* the object tasks' per-pair manifold kernels run one wave per SIMD at every batch: their
