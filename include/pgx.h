@@ -510,6 +510,114 @@ int pgx_replay_sample(pgx_replay_handle h, int64_t batch, uint64_t draw, pgx_rep
  * transitions after the last add() (i32 scalar), for tests / checkpoint / the host guard. */
 int pgx_replay_episode_arrays(pgx_replay_handle h, int32_t** ep_start, int32_t** ep_length, int32_t** n_valid);
 
+/* ------------------------------------------------------------------------
+ * VecNormalize: the observation / reward normalisation the reference's training
+ * settings turn on (classes/hyperparameters.py:42 `normalize = True`, :116), i.e.
+ * stable-baselines3's VecNormalize (stable_baselines3/common/vec_env/vec_normalize.py)
+ * over RunningMeanStd (common/running_mean_std.py), device-resident.
+ *
+ * Columns: C = obs_dim + 3 + 3 observation columns grouped by key -- observation,
+ * achieved_goal, desired_goal -- then one returns column (index C).  Per column fp64
+ * mean / var / count, RunningMeanStd(epsilon = 1e-4): mean 0, var 1, count 1e-4 at create;
+ * update(batch) with the batch's mean, population variance and count N:
+ *   delta = batch_mean - mean; tot = count + N; new_mean = mean + delta * N / tot;
+ *   M2 = var * count + batch_var * N + delta^2 * count * N / tot; new_var = M2 / tot; new_count = tot.
+ * Batch moments are accumulated in fp64 from the f32 inputs over fixed env slabs (mean, then
+ * squared deviations) and merged in slab order with Chan's (n, mean, M2) rule: the same bits
+ * in every run.  Outputs are clip((x - mean) / sqrt(var + epsilon), -clip, clip) and
+ * clip(reward / sqrt(ret_var + epsilon), -clip_reward, clip_reward), evaluated in fp64 without
+ * contraction and rounded once to f32: given the statistics, the bits numpy computes.
+ *
+ * pgx_norm_step and pgx_norm_reset are two kernel launches on `stream` each: no allocation,
+ * no synchronisation, no copy node, so they capture into a hipGraph behind pgx_step, and a
+ * captured sequence of any length replays correctly (which half of the statistics pair is
+ * current, and whether statistics move, are device words).
+ * ---------------------------------------------------------------------- */
+typedef struct pgx_norm* pgx_norm_handle;
+
+#define PGX_NORM_KEY_OBSERVATION 1   /* pgx_norm_config.key_mask bits (VecNormalize norm_obs_keys) */
+#define PGX_NORM_KEY_ACHIEVED_GOAL 2
+#define PGX_NORM_KEY_DESIRED_GOAL 4
+#define PGX_NORM_KEY_ALL 7
+/* pgx_norm_apply keys: 0 observation, 1 achieved_goal, 2 desired_goal, and */
+#define PGX_NORM_REWARD 3
+
+typedef struct pgx_norm_config {
+    int32_t n_envs;
+    int32_t obs_dim;              /* <= 249 */
+    int32_t key_mask;             /* PGX_NORM_KEY_* of the normalised keys; 0 = norm_obs False */
+    int32_t norm_reward;
+    double clip_obs;              /* VecNormalize defaults: 10 */
+    double clip_reward;           /* 10 */
+    double gamma;                 /* 0.99 */
+    double epsilon;               /* 1e-8 */
+} pgx_norm_config;
+
+/* Device pointers of one step (or reset).  Inputs are the raw step outputs (pgx_step_out's
+ * buffers) and are never written; outputs are separate buffers, any may be NULL to skip.
+ * flags / out_flags (optional): [flag_rows][N] u8 copied unchanged, so a host path fetches a whole
+ * normalised step with one copy. */
+typedef struct pgx_norm_io {
+    const float* obs;                     /* [N,obs_dim] */
+    const float* achieved_goal;           /* [N,3] */
+    const float* desired_goal;            /* [N,3] */
+    const float* reward;                  /* [N] (step only) */
+    const uint8_t* terminated;            /* [N] (step only) */
+    const uint8_t* truncated;             /* [N] (step only) */
+    const float* terminal_obs;            /* step only, may be NULL: rows of done envs are normalised */
+    const float* terminal_achieved_goal;
+    const float* terminal_desired_goal;
+    const uint8_t* flags;
+    float* out_obs;
+    float* out_achieved_goal;
+    float* out_desired_goal;
+    float* out_reward;
+    float* out_terminal_obs;              /* written only for envs with terminated | truncated */
+    float* out_terminal_achieved_goal;
+    float* out_terminal_desired_goal;
+    uint8_t* out_flags;
+    int32_t flag_rows;
+    int32_t pad0;
+} pgx_norm_io;
+
+/* VecNormalize.__init__ (training on).  PGX_E_INVALID, before any device call, for n_envs <= 0,
+ * obs_dim outside [1, 249], epsilon < 0, clips <= 0, gamma < 0 or unknown key bits. */
+int pgx_norm_create(const pgx_norm_config* cfg, int device, pgx_norm_handle* out);
+void pgx_norm_destroy(pgx_norm_handle h);
+/* VecNormalize.step_wait, in its order: (training) update the enabled keys' statistics from the
+ * step's observation rows -- the post-auto-reset ones; write the normalised observations (keys
+ * not enabled: copied); returns = returns * gamma + reward (fp64 per env; here also while not
+ * training), (training) update the returns statistics from them, write the normalised (or, without
+ * norm_reward, raw) reward; normalise the terminal_* rows of done envs with the updated
+ * statistics; returns[done] = 0. */
+int pgx_norm_step(pgx_norm_handle h, const pgx_norm_io* io, void* stream);
+/* VecNormalize.reset: returns = 0, (training) update from the reset observations, write them
+ * normalised.  Reads obs / achieved_goal / desired_goal and the out_* of those only. */
+int pgx_norm_reset(pgx_norm_handle h, const pgx_norm_io* io, void* stream);
+/* HerReplayBuffer.sample(batch_size, env=vec_normalize) -> _normalize_obs / _normalize_reward
+ * (stable_baselines3/her/her_replay_buffer.py): a sampled batch rows [batch, row_stride] in the
+ * layout above (pgx_replay_batch), in place, one launch, current statistics, no update.  obs /
+ * next_obs and the four goal fields by their keys' statistics (enabled keys only), reward by the
+ * returns statistics (with norm_reward); action, done and the row padding untouched. */
+int pgx_norm_rows(pgx_norm_handle h, float* rows, int64_t batch, int32_t action_dim, int32_t row_stride, void* stream);
+/* VecNormalize.normalize_obs / unnormalize_obs (one key) and normalize_reward /
+ * unnormalize_reward (key = PGX_NORM_REWARD, width 1) over in / out [m, width] f32 (may alias),
+ * stateless and whatever the key mask says.  inverse: x * sqrt(var + epsilon) + mean (rewards:
+ * without the mean), unclipped as in SB3. */
+int pgx_norm_apply(pgx_norm_handle h, int32_t key, int32_t inverse, const float* in, float* out, int64_t m, void* stream);
+/* VecNormalize.training: a device word switched on `stream`, so a captured step loop follows the
+ * value of replay time.  0 freezes every statistic. */
+int pgx_norm_set_training(pgx_norm_handle h, int32_t training, void* stream);
+/* VecNormalize.norm_obs / norm_obs_keys / norm_reward after create (host side: a captured graph keeps
+ * the values of capture time). */
+int pgx_norm_set_keys(pgx_norm_handle h, int32_t key_mask, int32_t norm_reward);
+/* VecNormalize.obs_rms / ret_rms / returns (and save / load): host arrays mean, var, count
+ * [obs_dim + 7] (the returns column last; the columns of a key share its count) and returns
+ * [n_envs] (may be NULL).  Both synchronise `stream`. */
+int pgx_norm_get_stats(pgx_norm_handle h, double* mean, double* var, double* count, double* returns, void* stream);
+int pgx_norm_set_stats(pgx_norm_handle h, const double* mean, const double* var, const double* count,
+                       const double* returns, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ C-ABI in include/pgx.h).  Public surface mirrors the reference's:
 from .envs import (Box, DictSpace, PandaEnv, PandaVecEnv, make, pcg64_from_record, pcg64_record, pcg64_records, register_envs,
                    registered_ids, seeded_goal, seeded_reset, spec, task_draws)
 from .her import HerReplayBuffer
+from .normalize import Normalizer, RunningMeanStd, VecNormalize
 from ._native import PgxError, load as load_native
 from .model import Model, load_model
 
@@ -19,4 +20,4 @@ __version__ = "0.1.0"
 
 __all__ = ["Box", "DictSpace", "PandaEnv", "PandaVecEnv", "make", "register_envs", "registered_ids",
            "seeded_goal", "seeded_reset", "spec", "task_draws", "pcg64_record", "pcg64_records", "pcg64_from_record", "PgxError", "load_native", "Model", "load_model",
-           "HerReplayBuffer"]
+           "HerReplayBuffer", "VecNormalize", "Normalizer", "RunningMeanStd"]

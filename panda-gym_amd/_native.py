@@ -9,7 +9,8 @@ import ctypes as C
 import os
 
 from .abi import PGX_E_INVALID  # noqa: F401 (re-exported for the C-ABI tests)
-from .abi import PgxConfig, PgxReplayBatch, PgxReplayConfig, PgxStateView, PgxStepOut, PgxTransition
+from .abi import (PgxConfig, PgxNormConfig, PgxNormIo, PgxReplayBatch, PgxReplayConfig, PgxStateView, PgxStepOut,
+                  PgxTransition)
 
 LIB_PATH = os.environ.get("PGX_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpgx.so")
 
@@ -20,6 +21,8 @@ EXPORTS = [
     "pgx_set_rng_streams", "pgx_get_rng_streams",
     "pgx_replay_create", "pgx_replay_destroy", "pgx_replay_add", "pgx_replay_size", "pgx_replay_sample",
     "pgx_replay_episode_arrays", "pgx_replay_row_dim", "pgx_replay_row_stride",
+    "pgx_norm_create", "pgx_norm_destroy", "pgx_norm_step", "pgx_norm_reset", "pgx_norm_rows", "pgx_norm_apply",
+    "pgx_norm_set_training", "pgx_norm_set_keys", "pgx_norm_get_stats", "pgx_norm_set_stats",
 ]
 
 
@@ -78,6 +81,17 @@ def load(path: str = None):
     lib.pgx_replay_sample.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(PgxReplayBatch), C.c_void_p]
     lib.pgx_replay_episode_arrays.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_void_p)]
+    lib.pgx_norm_create.argtypes = [C.POINTER(PgxNormConfig), C.c_int, C.POINTER(C.c_void_p)]
+    lib.pgx_norm_destroy.argtypes = [C.c_void_p]
+    lib.pgx_norm_destroy.restype = None
+    lib.pgx_norm_step.argtypes = [C.c_void_p, C.POINTER(PgxNormIo), C.c_void_p]
+    lib.pgx_norm_reset.argtypes = [C.c_void_p, C.POINTER(PgxNormIo), C.c_void_p]
+    lib.pgx_norm_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
+    lib.pgx_norm_apply.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.pgx_norm_set_training.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.pgx_norm_set_keys.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.pgx_norm_get_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pgx_norm_set_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _libs[path] = lib
     return lib
 

@@ -145,6 +145,33 @@ class PgxReplayBatch(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("slot", C.c_void_p), ("env", C.c_void_p), ("goal_slot", C.c_void_p)]
 
 
+# VecNormalize (include/pgx.h, pgx_norm_*): key bits of PgxNormConfig.key_mask in the order of the
+# columns, and pgx_norm_apply's key for rewards
+NORM_KEYS = ("observation", "achieved_goal", "desired_goal")
+NORM_KEY_BITS = {"observation": 1, "achieved_goal": 2, "desired_goal": 4}
+NORM_KEY_ALL = 7
+NORM_REWARD = 3
+
+
+class PgxNormConfig(C.Structure):
+    _fields_ = [
+        ("n_envs", C.c_int32), ("obs_dim", C.c_int32), ("key_mask", C.c_int32), ("norm_reward", C.c_int32),
+        ("clip_obs", C.c_double), ("clip_reward", C.c_double), ("gamma", C.c_double), ("epsilon", C.c_double),
+    ]
+
+
+class PgxNormIo(C.Structure):
+    _fields_ = [
+        ("obs", C.c_void_p), ("achieved_goal", C.c_void_p), ("desired_goal", C.c_void_p), ("reward", C.c_void_p),
+        ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("terminal_obs", C.c_void_p),
+        ("terminal_achieved_goal", C.c_void_p), ("terminal_desired_goal", C.c_void_p), ("flags", C.c_void_p),
+        ("out_obs", C.c_void_p), ("out_achieved_goal", C.c_void_p), ("out_desired_goal", C.c_void_p),
+        ("out_reward", C.c_void_p), ("out_terminal_obs", C.c_void_p), ("out_terminal_achieved_goal", C.c_void_p),
+        ("out_terminal_desired_goal", C.c_void_p), ("out_flags", C.c_void_p),
+        ("flag_rows", C.c_int32), ("pad0", C.c_int32),
+    ]
+
+
 def replay_row_fields(obs_dim: int, action_dim: int):
     """(name, offset, width) of the batch row layout of include/pgx.h, plus row_dim."""
     f, o = [], 0

@@ -189,7 +189,12 @@ class HerReplayBuffer:
         ``obs`` is a copy of the observation the action was taken from.  next_obs is
         the terminal observation for every env that was auto-reset, terminated or truncated
         (SB3 off_policy_algorithm _store_transition reads infos["terminal_observation"] of
-        any done env), dones = terminated | truncated, timeouts = truncated & ~terminated."""
+        any done env), dones = terminated | truncated, timeouts = truncated & ~terminated.
+
+        Given a ``VecNormalize`` wrapper, the raw values are stored (SB3 stores
+        ``get_original_obs()`` / ``get_original_reward()``): ``obs`` is the raw observation
+        (``get_original_obs(tensors=True)`` before the step) and the rest is read from the wrapped env."""
+        venv = getattr(venv, "venv", venv)
         tr = venv.truncated.bool()
         te = venv.terminated.bool()
         done = (tr | te).to(torch.uint8)
@@ -213,14 +218,16 @@ class HerReplayBuffer:
             out[k] = torch.empty((B,), dtype=torch.int32, device=self.device) if with_indices else None
         return out
 
-    def sample_raw(self, batch_size: int, draw: Optional[int] = None) -> Dict[str, "torch.Tensor"]:
+    def sample_raw(self, batch_size: int, draw: Optional[int] = None, env: Any = None) -> Dict[str, "torch.Tensor"]:
         """One relabelled batch: field views (obs, achieved_goal, ..., done) plus the drawn slot/env/goal_slot."""
         out = self.alloc_batch(batch_size)
-        self.sample_into(out, draw)
+        self.sample_into(out, draw, env=env)
         return out
 
-    def sample_into(self, out: Dict[str, "torch.Tensor"], draw: Optional[int] = None) -> None:
-        """Fill a batch from alloc_batch() (no allocation; the benchmark's timed call)."""
+    def sample_into(self, out: Dict[str, "torch.Tensor"], draw: Optional[int] = None, env: Any = None) -> None:
+        """Fill a batch from alloc_batch() (no allocation; the benchmark's timed call).  ``env``: a
+        ``VecNormalize`` whose current statistics normalise the batch in place (one more launch),
+        after the relabelled rewards were computed on the raw goals (SB3 _get_virtual_samples)."""
         rows = out["rows"]
         d = self._draw if draw is None else int(draw)
         self._draw = d + 1
@@ -235,10 +242,14 @@ class HerReplayBuffer:
                                    "a value for learning_starts that is greater than the maximum number of "
                                    "timesteps in the environment.")
             self._seen_valid = True
+        if env is not None:
+            env.normalize_rows(rows, self.action_dim)
 
     def sample(self, batch_size: int, env: Any = None) -> DictReplayBufferSamples:
-        """SB3 HerReplayBuffer.sample: real rows first, then int(her_ratio * B) relabelled rows."""
-        r = self.sample_raw(batch_size)
+        """SB3 HerReplayBuffer.sample: real rows first, then int(her_ratio * B) relabelled rows;
+        ``env`` (a ``VecNormalize``) normalises observations, goals and rewards as SB3's
+        ``sample(batch_size, env=vec_normalize)`` does."""
+        r = self.sample_raw(batch_size, env=env)
         return DictReplayBufferSamples(
             observations={"observation": r["obs"], "achieved_goal": r["achieved_goal"],
                           "desired_goal": r["desired_goal"]},
