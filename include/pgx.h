@@ -618,6 +618,111 @@ int pgx_norm_get_stats(pgx_norm_handle h, double* mean, double* var, double* cou
 int pgx_norm_set_stats(pgx_norm_handle h, const double* mean, const double* var, const double* count,
                        const double* returns, void* stream);
 
+/* ------------------------------------------------------------------------
+ * VecMonitor: the episode statistics every stable-baselines3 run has -- make_vec_env wraps
+ * each env in Monitor (the reference: training/utils/setup_training.py:43-47), whose
+ * infos[i]["episode"] = {"r", "l", "t"} feed rollout/ep_rew_mean, ep_len_mean and success_rate
+ * -- and the per-episode outcomes the reference's evaluation scores policies by
+ * (evaluation/evaluate.py:88-317 perform_benchmark; setup_training.py:310-318), device-resident.
+ * The arithmetic is stable_baselines3/common/vec_env/vec_monitor.py's.
+ *
+ * Per env: ret f32 (ret = ret + reward, one f32 add per step, as VecMonitor's float32
+ * episode_returns), len i32, speed f64 (the running sum of the step's end-effector speed
+ * sqrt(x*x + y*y + z*z), the three f32 columns obs[speed_col .. speed_col + 2] widened to fp64,
+ * products and sums left to right, no contraction; a done env's row is read from terminal_obs,
+ * the step's own observation, any other from obs), ep_count i32 (episodes recorded for the env).
+ *
+ * A finished episode (terminated | truncated) of an env below its target is recorded.  Its
+ * outcome, first match: PGX_EP_NONFINITE -- the step's nonfinite flag is set or ret is not finite;
+ * PGX_EP_SUCCESS -- the success flag; PGX_EP_COLLISION -- the task_truncated flag; PGX_EP_TIMEOUT
+ * (evaluate.py:250-267).  The records of one step are appended in ascending env id -- VecMonitor's
+ * `for i in range(len(dones))` -- to a ring of `window` records that keeps the newest `window`,
+ * as deque(maxlen = window) does (more than `window` in one step: the last `window` in env order).
+ * A record's `step` is the value of totals.steps after the step that finished it (the first
+ * pgx_monitor_step is step 1).  Done envs get ep_r[env] = ret and ep_l[env] = len (recorded or
+ * not), and their ret / len / speed go back to zero.
+ *
+ * Totals, over the recorded episodes: episodes and outcomes[code] count every one of them; the
+ * sums leave PGX_EP_NONFINITE episodes out (one poisoned env cannot turn them into NaN):
+ * length_sum and return_sum over the others, length_sum_success and speed_sum_success over the
+ * PGX_EP_SUCCESS ones (every step of a successful episode: mean EE speed = speed_sum_success /
+ * length_sum_success).  return_sum and speed_sum_success are fp64 sums of (double)ret and of
+ * speed in this order: envs are cut into fixed slabs (a multiple of 256 envs, at most 64 slabs);
+ * a slab's sum starts at 0.0 and adds its episodes in ascending env id; the step adds the slab
+ * sums to the running total in slab order, total = (..((total + slab_0) + slab_1) ..).  The same
+ * inputs give the same bits in every run.  steps counts pgx_monitor_step calls; envs_open the
+ * envs with ep_count < target (all of them without targets).
+ *
+ * pgx_monitor_step is two kernel launches on `stream`: no allocation, no synchronisation, no
+ * copy node, so it captures into a hipGraph behind pgx_step (and pgx_norm_step), and a captured
+ * sequence of any length replays correctly: the ring head, the step counter and which half of
+ * the totals pair is current are device words.
+ * ---------------------------------------------------------------------- */
+typedef struct pgx_monitor* pgx_monitor_handle;
+
+#define PGX_EP_TIMEOUT 0
+#define PGX_EP_SUCCESS 1
+#define PGX_EP_COLLISION 2
+#define PGX_EP_NONFINITE 3
+
+typedef struct pgx_monitor_config {
+    int32_t n_envs;
+    int32_t obs_dim;
+    int32_t window;               /* records the ring retains (SB3 stats_window_size: 100) */
+    int32_t speed_col;            /* first of the three EE-velocity columns of obs (3 in every task
+                                     here); < 0: no speed sums, obs / terminal_obs are not read */
+} pgx_monitor_config;
+
+/* Device pointers of one step: pgx_step_out's buffers, never written, and two optional outputs. */
+typedef struct pgx_monitor_io {
+    const float* reward;                  /* [N] */
+    const uint8_t* success;               /* [N] */
+    const uint8_t* terminated;            /* [N] */
+    const uint8_t* truncated;             /* [N] */
+    const float* obs;                     /* [N,obs_dim] (required with speed_col >= 0) */
+    const float* terminal_obs;            /* [N,obs_dim] (required with speed_col >= 0) */
+    const uint8_t* task_truncated;        /* [N], may be NULL: all 0 */
+    const uint8_t* nonfinite;             /* [N], may be NULL: all 0 */
+    float* ep_r;                          /* [N], may be NULL: the return of the episode an env finished */
+    int32_t* ep_l;                        /* [N], may be NULL: its length; both valid where done */
+} pgx_monitor_io;
+
+typedef struct pgx_monitor_totals {
+    int64_t episodes;
+    int64_t outcomes[4];                  /* by PGX_EP_* */
+    int64_t length_sum;
+    int64_t length_sum_success;
+    int64_t steps;
+    int64_t envs_open;
+    double return_sum;
+    double speed_sum_success;
+} pgx_monitor_totals;
+
+/* PGX_E_INVALID, before any device call, for n_envs <= 0, obs_dim <= 0, window outside
+ * [1, 2^24] or speed_col + 3 > obs_dim. */
+int pgx_monitor_create(const pgx_monitor_config* cfg, int device, pgx_monitor_handle* out);
+void pgx_monitor_destroy(pgx_monitor_handle h);
+/* VecMonitor.step_wait over one step's outputs, as described above. */
+int pgx_monitor_step(pgx_monitor_handle h, const pgx_monitor_io* io, void* stream);
+/* VecMonitor.reset for the envs with mask[env] != 0 (device [N] u8; NULL: all): ret, len and
+ * speed go to zero, the running episode is abandoned, not recorded.  One launch. */
+int pgx_monitor_reset(pgx_monitor_handle h, const uint8_t* mask, void* stream);
+/* Back to the state after create (accumulators, ring, totals, ep_count); targets stay. */
+int pgx_monitor_clear(pgx_monitor_handle h, void* stream);
+/* stable_baselines3 evaluate_policy's episode_count_targets: host int32 [N], each >= 0, or NULL
+ * for none.  An env with ep_count >= target keeps stepping (ep_r / ep_l are written, its
+ * accumulators cleared) but is not recorded, in the ring or in the totals.  Synchronises. */
+int pgx_monitor_set_targets(pgx_monitor_handle h, const int32_t* targets, void* stream);
+/* The current totals, after synchronising `stream`. */
+int pgx_monitor_get_totals(pgx_monitor_handle h, pgx_monitor_totals* out, void* stream);
+/* The newest min(max, retained) records, oldest first, into host arrays (any may be NULL);
+ * *count is their number.  Synchronises `stream`. */
+int pgx_monitor_read(pgx_monitor_handle h, int32_t max, float* r, int32_t* l, int32_t* env, int32_t* outcome,
+                     int64_t* step, double* speed_sum, int32_t* count, void* stream);
+/* The per-env state into host arrays [N] (any may be NULL).  Synchronises `stream`. */
+int pgx_monitor_get_env_state(pgx_monitor_handle h, float* ret, int32_t* len, double* speed, int32_t* ep_count,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

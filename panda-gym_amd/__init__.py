@@ -13,6 +13,7 @@ from .envs import (Box, DictSpace, PandaEnv, PandaVecEnv, make, pcg64_from_recor
                    registered_ids, seeded_goal, seeded_reset, spec, task_draws)
 from .her import HerReplayBuffer
 from .normalize import Normalizer, RunningMeanStd, VecNormalize
+from .monitor import EpisodeMonitor, VecMonitor, evaluate
 from ._native import PgxError, load as load_native
 from .model import Model, load_model
 
@@ -20,4 +21,5 @@ __version__ = "0.1.0"
 
 __all__ = ["Box", "DictSpace", "PandaEnv", "PandaVecEnv", "make", "register_envs", "registered_ids",
            "seeded_goal", "seeded_reset", "spec", "task_draws", "pcg64_record", "pcg64_records", "pcg64_from_record", "PgxError", "load_native", "Model", "load_model",
-           "HerReplayBuffer", "VecNormalize", "Normalizer", "RunningMeanStd"]
+           "HerReplayBuffer", "VecNormalize", "Normalizer", "RunningMeanStd",
+           "EpisodeMonitor", "VecMonitor", "evaluate"]

@@ -9,8 +9,8 @@ import ctypes as C
 import os
 
 from .abi import PGX_E_INVALID  # noqa: F401 (re-exported for the C-ABI tests)
-from .abi import (PgxConfig, PgxNormConfig, PgxNormIo, PgxReplayBatch, PgxReplayConfig, PgxStateView, PgxStepOut,
-                  PgxTransition)
+from .abi import (PgxConfig, PgxMonitorConfig, PgxMonitorIo, PgxMonitorTotals, PgxNormConfig, PgxNormIo, PgxReplayBatch,
+                  PgxReplayConfig, PgxStateView, PgxStepOut, PgxTransition)
 
 LIB_PATH = os.environ.get("PGX_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpgx.so")
 
@@ -23,6 +23,8 @@ EXPORTS = [
     "pgx_replay_episode_arrays", "pgx_replay_row_dim", "pgx_replay_row_stride",
     "pgx_norm_create", "pgx_norm_destroy", "pgx_norm_step", "pgx_norm_reset", "pgx_norm_rows", "pgx_norm_apply",
     "pgx_norm_set_training", "pgx_norm_set_keys", "pgx_norm_get_stats", "pgx_norm_set_stats",
+    "pgx_monitor_create", "pgx_monitor_destroy", "pgx_monitor_step", "pgx_monitor_reset", "pgx_monitor_clear",
+    "pgx_monitor_set_targets", "pgx_monitor_get_totals", "pgx_monitor_read", "pgx_monitor_get_env_state",
 ]
 
 
@@ -92,6 +94,16 @@ def load(path: str = None):
     lib.pgx_norm_set_keys.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.pgx_norm_get_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pgx_norm_set_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pgx_monitor_create.argtypes = [C.POINTER(PgxMonitorConfig), C.c_int, C.POINTER(C.c_void_p)]
+    lib.pgx_monitor_destroy.argtypes = [C.c_void_p]
+    lib.pgx_monitor_destroy.restype = None
+    lib.pgx_monitor_step.argtypes = [C.c_void_p, C.POINTER(PgxMonitorIo), C.c_void_p]
+    lib.pgx_monitor_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pgx_monitor_clear.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pgx_monitor_set_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pgx_monitor_get_totals.argtypes = [C.c_void_p, C.POINTER(PgxMonitorTotals), C.c_void_p]
+    lib.pgx_monitor_read.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.POINTER(C.c_int32), C.c_void_p]
+    lib.pgx_monitor_get_env_state.argtypes = [C.c_void_p] * 6
     _libs[path] = lib
     return lib
 

@@ -172,6 +172,31 @@ class PgxNormIo(C.Structure):
     ]
 
 
+# VecMonitor (include/pgx.h, pgx_monitor_*): the outcome codes of a finished episode (PGX_EP_*)
+EP_TIMEOUT, EP_SUCCESS, EP_COLLISION, EP_NONFINITE = 0, 1, 2, 3
+EP_OUTCOMES = ("timeout", "success", "collision", "nonfinite")
+
+
+class PgxMonitorConfig(C.Structure):
+    _fields_ = [("n_envs", C.c_int32), ("obs_dim", C.c_int32), ("window", C.c_int32), ("speed_col", C.c_int32)]
+
+
+class PgxMonitorIo(C.Structure):
+    _fields_ = [
+        ("reward", C.c_void_p), ("success", C.c_void_p), ("terminated", C.c_void_p), ("truncated", C.c_void_p),
+        ("obs", C.c_void_p), ("terminal_obs", C.c_void_p), ("task_truncated", C.c_void_p), ("nonfinite", C.c_void_p),
+        ("ep_r", C.c_void_p), ("ep_l", C.c_void_p),
+    ]
+
+
+class PgxMonitorTotals(C.Structure):
+    _fields_ = [
+        ("episodes", C.c_int64), ("outcomes", C.c_int64 * 4), ("length_sum", C.c_int64),
+        ("length_sum_success", C.c_int64), ("steps", C.c_int64), ("envs_open", C.c_int64),
+        ("return_sum", C.c_double), ("speed_sum_success", C.c_double),
+    ]
+
+
 def replay_row_fields(obs_dim: int, action_dim: int):
     """(name, offset, width) of the batch row layout of include/pgx.h, plus row_dim."""
     f, o = [], 0

@@ -246,6 +246,7 @@ class PandaVecEnv(_VecEnvBase):
 
     metadata = {"render_modes": []}
     render_mode = None
+    _pre_sync = None   # set by VecMonitor.step_wait for its own call: runs before step_wait's synchronise
 
     def __init__(self, env_id: str = "PandaReach-v3", num_envs: int = 4096, device: Any = "cuda:0", seed: int = 0,
                  env_id_offset: int = 0, max_episode_steps: Optional[int] = None, auto_reset: bool = True,
@@ -543,14 +544,20 @@ class PandaVecEnv(_VecEnvBase):
                                           self._stream()), "pgx_sample_actions")
         return self._actions
 
-    def capture_steps(self, k: int, actions: Optional[torch.Tensor] = None):
+    def _enqueue_step(self, a: torch.Tensor, what: str = "pgx_step") -> None:
+        """The step's launch on the current stream and nothing else (no checks of ``a``, no host
+        counter): what the ``capture_steps`` loops of the env and of its wrappers enqueue."""
+        self._check(self.lib.pgx_step(self._h, C.c_void_p(a.data_ptr()), C.byref(self._out), self._stream()), what)
+
+    def capture_steps(self, k: int, actions: Optional[torch.Tensor] = None, after_step=None):
         """Capture ``k`` lockstep env steps into one HIP graph (torch.cuda.CUDAGraph); ``replay()``
         runs them with no host launch in between (graph capture of the step loop).
         ``actions``: a static [k, N, A] f32 device buffer step i reads (refill it between replays),
         or None: the device Philox random policy, drawn inside the graph with the step counters of
         capture time (every replay repeats those draws; the env state moves on).  The step's outputs
         land in the env's usual buffers (obs, reward, ... of the last captured step).  Capture runs
-        nothing: the state changes only on replay."""
+        nothing: the state changes only on replay.  ``after_step``: a callable that enqueues a
+        wrapper's launches behind every captured step (``VecMonitor.capture_steps``)."""
         if actions is not None:
             if tuple(actions.shape) != (k, self.num_envs, self.action_dim) or actions.dtype != torch.float32 \
                     or actions.device != self.device or not actions.is_contiguous():
@@ -562,8 +569,9 @@ class PandaVecEnv(_VecEnvBase):
         with torch.cuda.graph(g):
             for i in range(k):
                 a = actions[i] if actions is not None else self.sample_actions(base + i)
-                self._check(self.lib.pgx_step(self._h, C.c_void_p(a.data_ptr()), C.byref(self._out), self._stream()),
-                            "pgx_step (capture)")
+                self._enqueue_step(a, "pgx_step (capture)")
+                if after_step is not None:
+                    after_step()
         g._pgx_keep = actions   # the graph reads the buffer at replay
         return g
 
@@ -635,6 +643,8 @@ class PandaVecEnv(_VecEnvBase):
         # SB3's per-env infos list is built while the step kernel runs: a fresh dict per env copied
         # in C from the common template, the few envs whose flags differ patched after the sync
         infos: List[Dict[str, Any]] = list(map(dict.copy, [_INFO_TEMPLATES[0]] * self.num_envs))
+        if self._pre_sync is not None:   # a wrapper's launches and copies, ahead of the one sync
+            self._pre_sync()
         stream.synchronize()
         guard = self.nonfinite_mode != "off"
         if hs["errors"].item():

@@ -327,10 +327,15 @@ class VecNormalize:
         self._norm.step(self._io)
         return self._obs_out(), self._n["reward"], term, trunc, succ
 
-    def capture_steps(self, k: int, actions: Optional["torch.Tensor"] = None):
+    def _enqueue_step(self, a: "torch.Tensor", what: str = "pgx_step") -> None:
+        """The env step's launch and the normalisation's two, on the current stream."""
+        self.venv._enqueue_step(a, what)
+        self._norm.step(self._io)
+
+    def capture_steps(self, k: int, actions: Optional["torch.Tensor"] = None, after_step=None):
         """``PandaVecEnv.capture_steps`` with the normalisation behind every env step: one HIP graph
         of ``k`` x (env step, moments, apply).  Statistics move on replay, by the value ``training``
-        has then."""
+        has then.  ``after_step``: as in ``PandaVecEnv.capture_steps``."""
         v = self.venv
         if actions is not None:
             if tuple(actions.shape) != (k, v.num_envs, v.action_dim) or actions.dtype != torch.float32 \
@@ -343,9 +348,9 @@ class VecNormalize:
         with torch.cuda.graph(g):
             for i in range(k):
                 a = actions[i] if actions is not None else v.sample_actions(base + i)
-                v._check(v.lib.pgx_step(v._h, C.c_void_p(a.data_ptr()), C.byref(v._out), v._stream()),
-                         "pgx_step (capture)")
-                self._norm.step(self._io)
+                self._enqueue_step(a, "pgx_step (capture)")
+                if after_step is not None:
+                    after_step()
         g._pgx_keep = actions   # the graph reads the buffer at replay
         return g
 
@@ -399,6 +404,8 @@ class VecNormalize:
         hs["packed"].copy_(self._outbuf, non_blocking=True)   # every output and the flags, one DMA
         hs["errors"].copy_(hs["errors_dev"], non_blocking=True)
         infos: List[Dict[str, Any]] = list(map(dict.copy, [_INFO_TEMPLATES[0]] * v.num_envs))
+        if v._pre_sync is not None:   # a wrapper's launches and copies, ahead of the one sync
+            v._pre_sync()
         stream.synchronize()
         guard = v.nonfinite_mode != "off"
         if hs["errors"].item():
