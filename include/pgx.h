@@ -723,6 +723,147 @@ int pgx_monitor_read(pgx_monitor_handle h, int32_t max, float* r, int32_t* l, in
 int pgx_monitor_get_env_state(pgx_monitor_handle h, float* ret, int32_t* len, double* speed, int32_t* ep_count,
                               void* stream);
 
+/* ------------------------------------------------------------------------
+ * RolloutBuffer: the on-policy buffer stable-baselines3's OnPolicyAlgorithm.collect_rollouts
+ * fills and PPO.train reads (stable_baselines3/common/buffers.py DictRolloutBuffer; the
+ * reference imports PPO beside its off-policy algorithms, training/utils/setup_training.py:14),
+ * device-resident: n_steps x n_envs transitions, the GAE(lambda) pass, the time-limit bootstrap
+ * of collect_rollouts and get(batch_size)'s shuffled minibatches.
+ *
+ * Storage, one allocation per handle.  A transition's vector fields are one record of
+ * record_stride = round_up(obs_dim + 6 + action_dim, 32) floats,
+ *   observation[obs_dim] | achieved_goal[3] | desired_goal[3] | action[action_dim] | zero padding,
+ * records [n_steps][n_envs][record_stride]; its six scalars live in six dense f32 planes
+ * [n_steps][n_envs] -- reward, episode_start (0 / 1), value, log_prob, advantage, return -- so the
+ * GAE pass, one lane per env, reads consecutive envs from consecutive addresses.  The carry is
+ * what SB3 keeps in _last_obs / _last_episode_starts: observation [N,obs_dim], achieved_goal
+ * [N,3], desired_goal [N,3], episode_start [N] f32 (ones after create).  Device words: pos and a
+ * sticky errors word (PGX_ROLLOUT_ERR_*).  pos is kept once per workgroup of pgx_rollout_add's
+ * launch (each reads and advances its own copy, so no workgroup hands anything to another); the
+ * copies are equal between launches and the first one is "pos".
+ *
+ * Every entry point below but create / destroy / state / arrays is ONE kernel launch on `stream`:
+ * no memcpy or memset node, no allocation, no synchronisation, so it captures into a hipGraph
+ * behind pgx_step, and a captured fill replays correctly after pgx_rollout_reset.
+ *
+ * All arithmetic is f32, every operation rounded separately (no contraction):
+ *   add:  reward' = reward + (float)gamma * terminal_value   where truncated & ~terminated and
+ *         terminal_value is given (SB3 collect_rollouts' TimeLimit.truncated bootstrap)
+ *   compute_returns_and_advantage, per env, SB3's loop and operation order:
+ *     g = (float)gamma; gl = (float)(gamma * gae_lambda)   (the double product rounded once)
+ *     last = 0
+ *     for t = T-1 .. 0:
+ *       nnt = 1 - (t == T-1 ? dones : episode_start[t+1]);  nv = (t == T-1 ? last_values : value[t+1])
+ *       delta = (reward[t] + (g * nv) * nnt) - value[t]
+ *       last  = delta + (gl * nnt) * last
+ *       advantage[t] = last;  return[t] = last + value[t]
+ *
+ * Flat transition index p = env * n_steps + step (SB3 swap_and_flatten), M = n_steps * n_envs.
+ * pgx_rollout_permutation replaces np.random.permutation(M) (numpy's global stream: no reference
+ * value exists) by a pure function of (seed, epoch, M), a balanced 6-round Feistel network over
+ * [0, 4^k) with cycle walking; uint32 arithmetic throughout:
+ *   fmix(h): h ^= h>>16; h *= 0x85EBCA6B; h ^= h>>13; h *= 0xC2B2AE35; h ^= h>>16
+ *   s = fmix(lo32(seed) ^ 0x9E3779B9); s = fmix(s ^ hi32(seed)); s = fmix(s ^ lo32(epoch));
+ *   s = fmix(s ^ hi32(epoch))
+ *   key[r]: s = fmix(s + 0x9E3779B9 * (r + 1)), key[r] = s,   r = 0..5
+ *   k = max(1, (bitlength(max(M - 1, 1)) + 1) / 2);  mask = 2^k - 1
+ *   perm(i): x = i; repeat { L = x >> k; R = x & mask;
+ *                            6 times, r = 0..5: (L, R) = (R, L ^ (fmix(R * 0x9E3779B1 + key[r]) & mask));
+ *                            x = L << k | R } until x < M
+ * (x lies on a cycle of a bijection of [0, 4^k) that passes through i < M, so the walk ends.)
+ *
+ * Batch row layout (floats), row_dim = obs_dim + 6 + action_dim + 4, rows row_stride =
+ * round_up(row_dim, 4) apart:
+ *   observation[obs_dim] | achieved_goal[3] | desired_goal[3] | action[action_dim] |
+ *   old_value | old_log_prob | advantage | return
+ * ---------------------------------------------------------------------- */
+typedef struct pgx_rollout* pgx_rollout_handle;
+
+#define PGX_ROLLOUT_ERR_OVERFLOW 1   /* pgx_rollout_add on a full buffer: nothing stored */
+#define PGX_ROLLOUT_ERR_NOT_FULL 2   /* compute_returns_and_advantage with pos != n_steps: nothing written */
+#define PGX_ROLLOUT_ERR_INDEX 4      /* pgx_rollout_gather: an index outside [0, M), its row is zero */
+
+typedef struct pgx_rollout_config {
+    int32_t n_envs;
+    int32_t n_steps;              /* transitions per env (SB3 buffer_size) */
+    int32_t obs_dim;
+    int32_t action_dim;
+    double gamma;                 /* in [0, 1] */
+    double gae_lambda;            /* in [0, 1] */
+    uint64_t seed;                /* of the minibatch permutations */
+} pgx_rollout_config;
+
+/* Device pointers of one add: the step's action and the policy's outputs for it, then the step's
+ * results.  Nothing is written. */
+typedef struct pgx_rollout_io {
+    const float* action;                  /* [N,action_dim] */
+    const float* reward;                  /* [N] */
+    const float* value;                   /* [N] */
+    const float* log_prob;                /* [N] */
+    const float* terminal_value;          /* [N], may be NULL: no time-limit bootstrap */
+    const float* obs;                     /* [N,obs_dim] post-step observation (the next carry); NULL with */
+    const float* achieved_goal;           /* [N,3]        the two goals: the carry is left as it is       */
+    const float* desired_goal;            /* [N,3] */
+    const uint8_t* terminated;            /* [N], may be NULL: all 0 */
+    const uint8_t* truncated;             /* [N], may be NULL: all 0 */
+} pgx_rollout_io;
+
+/* A gathered minibatch: rows [B, row_stride] f32 in the layout above, 16-byte aligned. */
+typedef struct pgx_rollout_batch {
+    float* rows;
+} pgx_rollout_batch;
+
+/* Device views of everything stored, for tests and tools: records [T][N][record_stride], the
+ * planes [T][N], the carry, the words (pos: the first of the equal per-workgroup copies). */
+typedef struct pgx_rollout_views {
+    float* records;
+    float* reward;
+    float* episode_start;
+    float* value;
+    float* log_prob;
+    float* advantage;
+    float* returns;
+    float* last_obs;
+    float* last_achieved_goal;
+    float* last_desired_goal;
+    float* last_episode_start;
+    int32_t* pos;
+    uint32_t* errors;
+    int32_t record_stride;
+    int32_t pad0;
+} pgx_rollout_views;
+
+/* row_dim / row_stride of a batch row for this config (floats). */
+int pgx_rollout_row_dim(const pgx_rollout_config* cfg);
+int pgx_rollout_row_stride(const pgx_rollout_config* cfg);
+/* PGX_E_INVALID, before any device call, for n_envs, n_steps, obs_dim or action_dim <= 0,
+ * n_steps * n_envs >= 2^31, or gamma / gae_lambda outside [0, 1] (NaN included). */
+int pgx_rollout_create(const pgx_rollout_config* cfg, int device, pgx_rollout_handle* out);
+void pgx_rollout_destroy(pgx_rollout_handle h);
+/* At slot pos: the carry's observation dict and episode_start with io's action, reward (plus the
+ * bootstrap), value and log_prob; then carry = (io's observation dict, terminated | truncated) and
+ * pos += 1.  With pos == n_steps: nothing stored, the carry untouched, PGX_ROLLOUT_ERR_OVERFLOW. */
+int pgx_rollout_add(pgx_rollout_handle h, const pgx_rollout_io* io, void* stream);
+/* The GAE pass above.  last_values [N] f32; dones [N] f32 0 / 1, or NULL: the carry's
+ * episode_start.  With pos != n_steps: nothing written, PGX_ROLLOUT_ERR_NOT_FULL. */
+int pgx_rollout_compute_returns_and_advantage(pgx_rollout_handle h, const float* last_values, const float* dones,
+                                              void* stream);
+/* out[i] = perm(i), i in [0, M), int32, for this handle's seed and the given epoch. */
+int pgx_rollout_permutation(pgx_rollout_handle h, uint64_t epoch, int32_t* out, void* stream);
+/* rows[b] = the transition with flat index indices[b] (device int32 [batch]); an index outside
+ * [0, M) gives a row of zeros and PGX_ROLLOUT_ERR_INDEX. */
+int pgx_rollout_gather(pgx_rollout_handle h, const int32_t* indices, int64_t batch, const pgx_rollout_batch* out,
+                       void* stream);
+/* SB3 rollout_buffer.reset(): pos = 0; the carry stays. */
+int pgx_rollout_reset(pgx_rollout_handle h, void* stream);
+/* The carry (SB3 _last_obs / _last_episode_starts after env.reset()): episode_start [N] f32 0 / 1,
+ * or NULL: ones. */
+int pgx_rollout_set_last(pgx_rollout_handle h, const float* obs, const float* achieved_goal, const float* desired_goal,
+                         const float* episode_start, void* stream);
+/* pos and errors after synchronising `stream` (either may be NULL); clear != 0 zeroes errors. */
+int pgx_rollout_state(pgx_rollout_handle h, int32_t* pos, uint32_t* errors, int32_t clear, void* stream);
+int pgx_rollout_arrays(pgx_rollout_handle h, pgx_rollout_views* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ from .envs import (Box, DictSpace, PandaEnv, PandaVecEnv, make, pcg64_from_recor
 from .her import HerReplayBuffer
 from .normalize import Normalizer, RunningMeanStd, VecNormalize
 from .monitor import EpisodeMonitor, VecMonitor, evaluate
+from .rollout import RolloutBuffer, RolloutBufferSamples
 from ._native import PgxError, load as load_native
 from .model import Model, load_model
 
@@ -22,4 +23,4 @@ __version__ = "0.1.0"
 __all__ = ["Box", "DictSpace", "PandaEnv", "PandaVecEnv", "make", "register_envs", "registered_ids",
            "seeded_goal", "seeded_reset", "spec", "task_draws", "pcg64_record", "pcg64_records", "pcg64_from_record", "PgxError", "load_native", "Model", "load_model",
            "HerReplayBuffer", "VecNormalize", "Normalizer", "RunningMeanStd",
-           "EpisodeMonitor", "VecMonitor", "evaluate"]
+           "EpisodeMonitor", "VecMonitor", "evaluate", "RolloutBuffer", "RolloutBufferSamples"]

@@ -10,7 +10,8 @@ import os
 
 from .abi import PGX_E_INVALID  # noqa: F401 (re-exported for the C-ABI tests)
 from .abi import (PgxConfig, PgxMonitorConfig, PgxMonitorIo, PgxMonitorTotals, PgxNormConfig, PgxNormIo, PgxReplayBatch,
-                  PgxReplayConfig, PgxStateView, PgxStepOut, PgxTransition)
+                  PgxReplayConfig, PgxRolloutBatch, PgxRolloutConfig, PgxRolloutIo, PgxRolloutViews, PgxStateView, PgxStepOut,
+                  PgxTransition)
 
 LIB_PATH = os.environ.get("PGX_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpgx.so")
 
@@ -25,6 +26,9 @@ EXPORTS = [
     "pgx_norm_set_training", "pgx_norm_set_keys", "pgx_norm_get_stats", "pgx_norm_set_stats",
     "pgx_monitor_create", "pgx_monitor_destroy", "pgx_monitor_step", "pgx_monitor_reset", "pgx_monitor_clear",
     "pgx_monitor_set_targets", "pgx_monitor_get_totals", "pgx_monitor_read", "pgx_monitor_get_env_state",
+    "pgx_rollout_row_dim", "pgx_rollout_row_stride", "pgx_rollout_create", "pgx_rollout_destroy", "pgx_rollout_add",
+    "pgx_rollout_compute_returns_and_advantage", "pgx_rollout_permutation", "pgx_rollout_gather", "pgx_rollout_reset",
+    "pgx_rollout_set_last", "pgx_rollout_state", "pgx_rollout_arrays",
 ]
 
 
@@ -104,6 +108,19 @@ def load(path: str = None):
     lib.pgx_monitor_get_totals.argtypes = [C.c_void_p, C.POINTER(PgxMonitorTotals), C.c_void_p]
     lib.pgx_monitor_read.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.POINTER(C.c_int32), C.c_void_p]
     lib.pgx_monitor_get_env_state.argtypes = [C.c_void_p] * 6
+    lib.pgx_rollout_row_dim.argtypes = [C.POINTER(PgxRolloutConfig)]
+    lib.pgx_rollout_row_stride.argtypes = [C.POINTER(PgxRolloutConfig)]
+    lib.pgx_rollout_create.argtypes = [C.POINTER(PgxRolloutConfig), C.c_int, C.POINTER(C.c_void_p)]
+    lib.pgx_rollout_destroy.argtypes = [C.c_void_p]
+    lib.pgx_rollout_destroy.restype = None
+    lib.pgx_rollout_add.argtypes = [C.c_void_p, C.POINTER(PgxRolloutIo), C.c_void_p]
+    lib.pgx_rollout_compute_returns_and_advantage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pgx_rollout_permutation.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.pgx_rollout_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PgxRolloutBatch), C.c_void_p]
+    lib.pgx_rollout_reset.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pgx_rollout_set_last.argtypes = [C.c_void_p] * 6
+    lib.pgx_rollout_state.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int32, C.c_void_p]
+    lib.pgx_rollout_arrays.argtypes = [C.c_void_p, C.POINTER(PgxRolloutViews)]
     _libs[path] = lib
     return lib
 

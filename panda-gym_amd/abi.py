@@ -197,6 +197,52 @@ class PgxMonitorTotals(C.Structure):
     ]
 
 
+# RolloutBuffer (include/pgx.h, pgx_rollout_*): the bits of the sticky device error word (PGX_ROLLOUT_ERR_*)
+ROLLOUT_ERR_OVERFLOW, ROLLOUT_ERR_NOT_FULL, ROLLOUT_ERR_INDEX = 1, 2, 4
+ROLLOUT_ERRORS = {ROLLOUT_ERR_OVERFLOW: "PGX_ROLLOUT_ERR_OVERFLOW: add() on a full buffer (nothing was stored)",
+                  ROLLOUT_ERR_NOT_FULL: "PGX_ROLLOUT_ERR_NOT_FULL: compute_returns_and_advantage() before the buffer "
+                                        "was full (nothing was written)",
+                  ROLLOUT_ERR_INDEX: "PGX_ROLLOUT_ERR_INDEX: gather() index outside [0, n_steps * n_envs) (its row is zero)"}
+
+
+class PgxRolloutConfig(C.Structure):
+    _fields_ = [
+        ("n_envs", C.c_int32), ("n_steps", C.c_int32), ("obs_dim", C.c_int32), ("action_dim", C.c_int32),
+        ("gamma", C.c_double), ("gae_lambda", C.c_double), ("seed", C.c_uint64),
+    ]
+
+
+class PgxRolloutIo(C.Structure):
+    _fields_ = [
+        ("action", C.c_void_p), ("reward", C.c_void_p), ("value", C.c_void_p), ("log_prob", C.c_void_p),
+        ("terminal_value", C.c_void_p), ("obs", C.c_void_p), ("achieved_goal", C.c_void_p),
+        ("desired_goal", C.c_void_p), ("terminated", C.c_void_p), ("truncated", C.c_void_p),
+    ]
+
+
+class PgxRolloutBatch(C.Structure):
+    _fields_ = [("rows", C.c_void_p)]
+
+
+class PgxRolloutViews(C.Structure):
+    _fields_ = [
+        ("records", C.c_void_p), ("reward", C.c_void_p), ("episode_start", C.c_void_p), ("value", C.c_void_p),
+        ("log_prob", C.c_void_p), ("advantage", C.c_void_p), ("returns", C.c_void_p), ("last_obs", C.c_void_p),
+        ("last_achieved_goal", C.c_void_p), ("last_desired_goal", C.c_void_p), ("last_episode_start", C.c_void_p),
+        ("pos", C.c_void_p), ("errors", C.c_void_p), ("record_stride", C.c_int32), ("pad0", C.c_int32),
+    ]
+
+
+def rollout_row_fields(obs_dim: int, action_dim: int):
+    """(name, offset, width) of the RolloutBuffer batch row layout of include/pgx.h, plus row_dim."""
+    f, o = [], 0
+    for name, w in (("observation", obs_dim), ("achieved_goal", 3), ("desired_goal", 3), ("action", action_dim),
+                    ("old_value", 1), ("old_log_prob", 1), ("advantage", 1), ("return", 1)):
+        f.append((name, o, w))
+        o += w
+    return f, o
+
+
 def replay_row_fields(obs_dim: int, action_dim: int):
     """(name, offset, width) of the batch row layout of include/pgx.h, plus row_dim."""
     f, o = [], 0

@@ -269,11 +269,19 @@ class VecMonitor:
         self._mon.step(self._io)
         return out
 
-    def capture_steps(self, k: int, actions: Optional["torch.Tensor"] = None):
+    def capture_steps(self, k: int, actions: Optional["torch.Tensor"] = None, after_step=None):
         """The wrapped ``capture_steps`` with the monitor's launches behind every captured step.  The
         ring head, the step counter and the totals' parity are device words: any number of replays
-        records what the same steps run eagerly record."""
-        return self.venv.capture_steps(k, actions, after_step=self._enqueue_monitor)
+        records what the same steps run eagerly record.  ``after_step``: a further callable that
+        enqueues behind the monitor's launches (``RolloutBuffer.after_step``)."""
+        if after_step is None:
+            return self.venv.capture_steps(k, actions, after_step=self._enqueue_monitor)
+
+        def both() -> None:
+            self._enqueue_monitor()
+            after_step()
+
+        return self.venv.capture_steps(k, actions, after_step=both)
 
     # ------------------------------------------------------------- SB3 path
     def reset(self, seed: Optional[int] = None, options: Optional[dict] = None):
