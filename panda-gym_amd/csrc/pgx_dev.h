@@ -81,8 +81,9 @@ struct PgxDevEnv {
     int32_t lanes_per_env;         /* step layout: 1 (env per lane) or 16 (env per DPP row) */
     int32_t pgs_mode;              /* test hook (PGX_PGS_MODE): 0 auto, 2 never speculate on the limit
                                       rows, 3 always redo the speculative solve with them, 4 auto but
-                                      never the merged-register sweeps of the arm kernels (substep_g's
-                                      MERGE: the two-register sweeps, bit-identical by claim) */
+                                      the general instance of the contact part in every wave, never
+                                      merged (the arm kernels' two-point instance and substep_g's MERGE
+                                      off: the two-register sweeps, bit-identical by claim) */
     int32_t n_substeps;            /* stepSimulation calls per env step (a runtime loop count) */
     int32_t full_manifold;         /* contacts == PGX_CONTACTS_FULL: robot budget PGX_ROBOT_POINTS(_ARM) */
     int32_t wave_mode;             /* A/B hook (PGX_WAVES_PER_SIMD): 0 auto (two resident waves per SIMD

@@ -454,6 +454,16 @@ __device__ __forceinline__ void chol7(float A[NJ][NJ]) {
         }
     }
 }
+/* L^T x = y (the second half of chol7_solve) */
+__device__ __forceinline__ void chol7_back(const float L[NJ][NJ], const float* y, float* x) {
+#pragma unroll
+    for (int i = NJ - 1; i >= 0; i--) {
+        float s = y[i];
+#pragma unroll
+        for (int k = i + 1; k < NJ; k++) s -= L[k][i] * x[k];
+        x[i] = s * L[i][i];
+    }
+}
 __device__ __forceinline__ void chol7_solve(const float L[NJ][NJ], const float* b, float* x) {
     float y[NJ];
 #pragma unroll
@@ -463,13 +473,40 @@ __device__ __forceinline__ void chol7_solve(const float L[NJ][NJ], const float* 
         for (int k = 0; k < i; k++) s -= L[i][k] * y[k];
         y[i] = s * L[i][i];
     }
-#pragma unroll
-    for (int i = NJ - 1; i >= 0; i--) {
-        float s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < NJ; k++) s -= L[k][i] * x[k];
-        x[i] = s * L[i][i];
-    }
+    chol7_back(L, y, x);
+}
+/* chol7 and chol7_solve's forward substitution with row i of the system on lane i of the env's
+ * 16-lane row: a[k] = A[i][k] (k <= i; what the entries k > i and the lanes >= 7 hold is never
+ * used) and b = b_i.  Column j: lane i subtracts L[i][k] L[j][k], k ascending, L[j][k] broadcast
+ * from lane j; lane j's result is the diagonal, so one rsq per column and one multiply per lane
+ * instead of the redundant factorisation's 84 operations on every lane.  The factor is then
+ * broadcast to every lane (L, the diagonal inverted as chol7 stores it) for the back
+ * substitution, and y_k = s_k L[k][k]^-1 is broadcast as lane i subtracts L[i][k] y_k.  Every
+ * product and every accumulation order is chol7's / chol7_solve's: the same bits. */
+__device__ __forceinline__ void chol7_rows(float* a, float b, float L[NJ][NJ], float* y) {
+    sfor<0, NJ>([&](auto jc) __attribute__((always_inline)) {
+        constexpr int j = decltype(jc)::value;
+        float t = a[j];
+        sfor<0, j>([&](auto kc) __attribute__((always_inline)) {
+            constexpr int k = decltype(kc)::value;
+            t -= a[k] * bcast16<j>(a[k]);
+        });
+        const float inv = __builtin_amdgcn_rsqf(fmaxf(bcast16<j>(t), 1e-30f));
+        L[j][j] = inv;
+        a[j] = t * inv;   /* L[i][j] on the lanes i > j */
+    });
+    sfor<0, NJ>([&](auto ic) __attribute__((always_inline)) {
+        constexpr int i = decltype(ic)::value;
+        sfor<0, i>([&](auto kc) __attribute__((always_inline)) {
+            constexpr int k = decltype(kc)::value;
+            L[i][k] = bcast16<i>(a[k]);
+        });
+    });
+    sfor<0, NJ>([&](auto kc) __attribute__((always_inline)) {
+        constexpr int k = decltype(kc)::value;
+        y[k] = bcast16<k>(b) * L[k][k];
+        b -= a[k] * y[k];
+    });
 }
 
 /* calculateInverseKinematics(link 11, pos, orn=[1,0,0,0]) as the reference
@@ -515,9 +552,9 @@ __device__ __forceinline__ void ik(MPtr mp, const float* q0, V3 target, const fl
         float A[NJ][NJ], g[NJ], dth[NJ];
         if constexpr (PAR) {
             /* the normal equations across the env's row: lane c < 7 holds Jacobian column c, forms
-             * row c of J^T J (column b broadcast from lane b) and g_c, and the row broadcasts the
-             * lower triangle back to every lane for the (redundant) Cholesky.  The same products
-             * in the same order as the per-lane form below, so the same bits. */
+             * row c of J^T J (column b broadcast from lane b) and g_c, and the row factors the
+             * matrix where its rows are (chol7_rows).  The same products in the same order as
+             * the per-lane form below, so the same bits. */
             V3 zs[NJ], os[NJ];
 #pragma unroll
             for (int j = 0; j < NJ; j++) { zs[j] = col(k.R[j], 2); os[j] = k.o[j]; }
@@ -530,15 +567,13 @@ __device__ __forceinline__ void ik(MPtr mp, const float* q0, V3 target, const fl
                 const V3 jwb = v3(bcast16<b>(jwc.x), bcast16<b>(jwc.y), bcast16<b>(jwc.z));
                 Ac[b] = dot(jvc, jvb) + dot(jwc, jwb);
             });
-            sfor<0, NJ>([&](auto ac) __attribute__((always_inline)) {
-                constexpr int a = decltype(ac)::value;
-                g[a] = bcast16<a>(gc);
-                sfor<0, a + 1>([&](auto bc) __attribute__((always_inline)) {
-                    constexpr int b = decltype(bc)::value;
-                    A[a][b] = bcast16<a>(Ac[b]);
-                });
-                A[a][a] += m.ik_damping;
+            /* the damping on lane b's own diagonal entry (x + -0 = x elsewhere, zeros included) */
+            sfor<0, NJ>([&](auto bc) __attribute__((always_inline)) {
+                constexpr int b = decltype(bc)::value;
+                Ac[b] += lane_sel<b>(m.ik_damping, -0.0f);
             });
+            chol7_rows(Ac, gc, A, g);   /* g: the forward substitution's y */
+            chol7_back(A, g, dth);
         } else {
             V3 jv[NJ], jw[NJ];
 #pragma unroll
@@ -553,9 +588,9 @@ __device__ __forceinline__ void ik(MPtr mp, const float* q0, V3 target, const fl
                 for (int b = 0; b <= a; b++) A[a][b] = dot(jv[a], jv[b]) + dot(jw[a], jw[b]);
                 A[a][a] += m.ik_damping;
             }
+            chol7(A);
+            chol7_solve(A, g, dth);
         }
-        chol7(A);
-        chol7_solve(A, g, dth);
         float mx = 0.0f;
 #pragma unroll
         for (int j = 0; j < NJ; j++) mx = fmaxf(mx, fabsf(dth[j]));
@@ -2287,15 +2322,10 @@ __device__ __forceinline__ void substep_dyn_g(MRef m, const PgxDevEnv& e, const 
     const V3 Fs = row_suf(link_only(F));
     const V3 Ms = row_suf(link_only(T + cross(cb, F)));
     const float nbl = -dot(zl, Ms - cross(ob_l, Fs));
-    float nb[NJ];
-    sfor<0, NJ>([&](auto jc) __attribute__((always_inline)) {
-        constexpr int j = decltype(jc)::value;
-        nb[j] = bcast16<j>(nbl);
-    });
     PGX_PROF_MARK(14);
 
     /* ---- mass matrix (CRBA) by suffix sums of mass, first moment and base-referred inertia */
-    float Mt[NJ][NJ];
+    float Mt[NJ][NJ], yb[NJ];
     {
         const float ml = link_only(K.mass);
         const S3 st = steiner(ml, cb);
@@ -2311,19 +2341,13 @@ __device__ __forceinline__ void substep_dyn_g(MRef m, const PgxDevEnv& e, const 
         float colv[NJ];
 #pragma unroll
         for (int i = 0; i < NJ; i++) colv[i] = dot(z[i], n + cross(ol - o[i], f));   /* M[c][i], i <= c */
-        sfor<0, NJ>([&](auto jc) __attribute__((always_inline)) {
-            constexpr int j = decltype(jc)::value;
-            sfor<0, j + 1>([&](auto ic) __attribute__((always_inline)) {
-                constexpr int i = decltype(ic)::value;
-                Mt[j][i] = bcast16<j>(colv[i]);
-            });
-        });
+        /* factored where the rows are, with the bias nbl's forward substitution */
+        chol7_rows(colv, nbl, Mt, yb);
     }
-    chol7(Mt);
     float (&vu)[NJ] = D.vu;
     {
         float qdd[NJ];
-        chol7_solve(Mt, nb, qdd);
+        chol7_back(Mt, yb, qdd);
 #pragma unroll
         for (int j = 0; j < NJ; j++) vu[j] = fminf(fmaxf(qd[j] + m.dt * qdd[j], -m.max_vel), m.max_vel);
     }
@@ -2894,11 +2918,47 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
     const float vu_c = pick_gen(vu, vcu, wcu);
     float gv = 0.0f;   /* this lane's velocity delta */
 
+    /* The contact part (row setup, solve, integration, cache) is one instance per count of register
+     * points, cgr_c.  Every kernel has the general instance (CGR_ALL points, the extra rows past
+     * them).  The kernels that merge (MERGE below: arm tasks, one wave per SIMD) have a two-point
+     * instance beside it, taken by a wave whose envs hold at most 2 robot points each (none
+     * included): every per-point object has two entries there, NQ is 6, and nothing touches a point
+     * past 1 (but the warm-start lookup) -- in the general instance such a wave pays, per substep, for
+     * the loads, zero fills, dead transpose rows, scaled-unit prologue and cache slots of two
+     * absent points, and the four-point arrays set the kernel's register peak.  An absent point's
+     * rows are zero rows in the general instance (J = R = 0, lambda = 0, bounds [0, 0]; the
+     * 2-point sweep copies never ran them), so the two-point instance computes the same bits
+     * (tests/test_gpu_two_point_path.py: PGX_PGS_MODE=4 is "the general instance, never merged").
+     * The choice is wave-uniform, made after detection (below, where contact_part ends), outside
+     * every loop.  (The lambda's text keeps substep_g's indentation.) */
+    constexpr int CGR_ALL = ContactLdsGT<OBJ, FULL>::CGR;   /* robot points with register (Delassus) rows */
+    constexpr bool MERGE_K = CONT && !OBJ && !AO && ((AO ? PGX_PK_AO : PGX_PK) & 3) == 0 && PART != 2;
+    /* PGX_CONTACT_INPLACE (the object and ReachAO units, PGX_TU 2 and 4: general instance only): the
+     * contact part as plain statements of substep_g -- wrapped in the lambda those kernels compiled
+     * to other code (register allocation, sweep copies), as with pgx_limit_solves.inc.  For a
+     * register report of such a kernel: tools/ru_one.sh KERNEL -DPGX_CONTACT_INPLACE=1 */
+#ifndef PGX_CONTACT_INPLACE
+#if defined(PGX_TU) && (PGX_TU == 2 || PGX_TU == 4)
+#define PGX_CONTACT_INPLACE 1
+#else
+#define PGX_CONTACT_INPLACE 0
+#endif
+#endif
+#if PGX_CONTACT_INPLACE
+    static_assert(!MERGE_K, "a kernel that merges needs the instances (not PGX_CONTACT_INPLACE)");
+    const IC<CGR_ALL> cgr_c{};
+    {
+#else
+    auto contact_part = [&](auto cgr_c) __attribute__((always_inline)) {
+#endif
     /* ---- contact rows: per lane J_c and (M^-1 J^T)_c, per row rhs / jinv / den / lambda */
     constexpr int P0 = OBJ ? CG : 0;            /* group-1 rows follow group 0's */
-    constexpr int CGR = ContactLdsGT<OBJ, FULL>::CGR;   /* robot points with register (Delassus) rows */
+    constexpr int CGR = decltype(cgr_c)::value;   /* this instance's register points */
+    constexpr bool TWOPT = CGR < CGR_ALL;         /* the two-point instance: no point past CGR in the wave */
+    static_assert(!TWOPT || (MERGE_K && CGR == 2), "the two-point instance belongs to the kernels that merge");
     constexpr int NP = P0 + (CONT ? CGR : 0);
-    constexpr int RB = CONT ? ContactLdsGT<OBJ, FULL>::RB : CGR;   /* robot budget: points CGR.. are the extra rows */
+    constexpr int RB_ALL = CONT ? ContactLdsGT<OBJ, FULL>::RB : CGR_ALL;   /* robot budget: the cache's robot slots */
+    constexpr int RB = TWOPT ? CGR : RB_ALL;      /* points CGR..RB-1 are the extra rows */
     constexpr int NQR = ContactLdsGT<OBJ, FULL>::NQR;
     constexpr int NC_ = OBJ ? 13 : NJ;          /* generalized coordinates in lanes */
     /* extra points run in the sweep: multiples of XSTEP, one sweep copy per multiple (round 4:
@@ -2920,14 +2980,16 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
         n1 = L.cnt[1][es];
         const float erp_dt = m.contact_erp * m.inv_dt;
         /* the warm-start cache slots, read once for every point (ids, impulses) */
-        float cid0[CG], cim0[CG], cid1[CGR], cim1[CGR];
+        /* (CGR_ALL robot slots in the two-point instance too: they are the previous substep's, which
+         * may have held this substep's point in a later slot -- two points of lower id gone) */
+        float cid0[CG], cim0[CG], cid1[CGR_ALL], cim1[CGR_ALL];
 #pragma unroll
         for (int s2 = 0; s2 < CG; s2++) {
             cid0[s2] = OBJ ? L.cache[2 * s2][es] : -1.0f;
             cim0[s2] = OBJ ? L.cache[2 * s2 + 1][es] : 0.0f;
         }
 #pragma unroll
-        for (int s2 = 0; s2 < CGR; s2++) {
+        for (int s2 = 0; s2 < CGR_ALL; s2++) {
             cid1[s2] = L.cache[CACHE1 + 2 * s2][es];
             cim1[s2] = L.cache[CACHE1 + 2 * s2 + 1][es];
         }
@@ -2994,7 +3056,7 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
         /* a manifold point's warm start is its own applied impulse (btManifoldPoint::m_appliedImpulse
          * x the warm-starting factor), a fresh table point's its feature's cached one */
         auto warm_pt = [&](int w, float id) __attribute__((always_inline)) {
-            return (PERS && w >= 0) ? m.warmstart * L.mimp[w < 0 ? 0 : w][es] : warm_of(cid1, cim1, IC<CGR>{}, id);
+            return (PERS && w >= 0) ? m.warmstart * L.mimp[w < 0 ? 0 : w][es] : warm_of(cid1, cim1, IC<CGR_ALL>{}, id);
         };
         /* (ReachAO: points are rare and the o2 kernel's registers scarce: read per point) */
         if (!AO && __any(n1 > 0)) {
@@ -3329,6 +3391,7 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
      * its frame grows from 232 to 240 B of scratch per lane -- another whole-kernel value spilled at
      * entry -- in every variant tried; it keeps the two-register sweeps) */
     constexpr bool MERGE = WROWS && !OBJ && !AO && !PKM && !PKC && PART != 2;
+    static_assert(MERGE == MERGE_K, "MERGE_K (the instances' choice) restates MERGE");
     constexpr int MG0 = 8;
     static_assert(!MERGE || MG0 + 6 <= GW, "6 contact rows from lane MG0");
     auto hi_sel = [&](float a, float other) __attribute__((always_inline)) {   /* lanes MG0.. take a */
@@ -3744,9 +3807,12 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
     /* the robot point count fixed at compile time (above) for every mode but far; the extra
      * points (past CGR) only in the speculative and all-rows solves (the partial one hands a wave
      * with extra points to the all-rows solve) */
-    /* merged sweeps for this wave (MERGE, above): a wave-uniform choice outside the sweep loop;
-     * PGX_PGS_MODE=4 is "auto, but never merge" (the two-register sweeps, for A/B tests) */
-    const bool mg = MERGE && e.pgs_mode != 4 && n1w >= 1 && n1w <= 2 && nxr == 0;
+    /* merged sweeps for this wave (MERGE, above): a wave-uniform choice outside the sweep loop.
+     * Only the two-point instance merges: the general one holds a wave with 3 or more points
+     * somewhere, or runs under PGX_PGS_MODE=4 ("the general instance, never merged", for A/B
+     * tests: the shipped library reaches the general instance's two-register 2-point copies only
+     * under that mode) */
+    const bool mg = TWOPT && n1w >= 1;
     auto merge_rows = [&]() __attribute__((always_inline)) {
         if constexpr (MERGE) {
 #pragma unroll
@@ -3774,6 +3840,11 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
         const IC<0> m0{};
         if constexpr (decltype(mgi_c)::value) {
             solve(mode_c, IC<2>{}, k_c, IC<0>{}, IC<(MODE != 2) ? 1 : 0>{});
+        } else if constexpr (TWOPT) {
+            /* the two-point instance's unmerged solves: a wave without points (its limit-row
+             * solves), or all rows from the start (PGX_PGS_MODE=2) */
+            if (MODE != 2 || n1w == 0) solve(mode_c, IC<0>{}, k_c, IC<0>{}, m0);
+            else solve(mode_c, IC<2>{}, k_c, IC<0>{}, m0);
         } else if constexpr (WROWS) {
             /* (n1w counts register points only: a wave with extra points has n1w = CGR, which is 2
              * for the arm tasks, so the extra-point copies are chosen by nxr first) */
@@ -3858,8 +3929,12 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
                 auto limit_solves = [&](auto mgi_c) __attribute__((always_inline)) {
 #include "pgx_limit_solves.inc"
                 };
-                if (mg) limit_solves(IC<1>{});
-                else limit_solves(IC<0>{});
+                if constexpr (TWOPT) {   /* (IC<0>: a wave without points, the no-point copies) */
+                    if (mg) limit_solves(IC<1>{});
+                    else limit_solves(IC<0>{});
+                } else {
+                    limit_solves(IC<0>{});
+                }
             } else {
                 const IC<0> mgi_c{};
 #include "pgx_limit_solves.inc"
@@ -3925,6 +4000,13 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
                 L.cache[CACHE1 + 2 * s + 1][es] = s < n1 ? L.xlam[xq][es] * L.xjinv[xq][es] : 0.0f;
             }
         }
+        if constexpr (TWOPT) {   /* no env of the wave holds a point past 1: the other slots are empty */
+#pragma unroll
+            for (int s = CGR; s < RB_ALL; s++) {
+                L.cache[CACHE1 + 2 * s][es] = -1.0f;
+                L.cache[CACHE1 + 2 * s + 1][es] = 0.0f;
+            }
+        }
         if constexpr (PERS) {   /* the solved normal impulse back to its manifold point (writeBackContacts):
                                  * lane c takes slot c (each point feeds one slot, so no two lanes write
                                  * the same word) */
@@ -3936,6 +4018,20 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
             }
         }
     }
+#if PGX_CONTACT_INPLACE
+    }
+#else
+    };   /* contact_part */
+    if constexpr (MERGE_K) {
+        /* the wave's largest robot point count <= 2 (a wave without points too); PGX_PGS_MODE=4
+         * keeps every wave in the general instance */
+        const bool two = e.pgs_mode != 4 && !__any(Lp->cnt[1][es] > 2);
+        if (two) contact_part(IC<2>{});
+        else contact_part(IC<CGR_ALL>{});
+    } else {
+        contact_part(IC<CGR_ALL>{});
+    }
+#endif
     if (OBJ) {
         const V3 dvl = v3(bcast16<7>(gv), bcast16<8>(gv), bcast16<9>(gv));
         const V3 dvw = v3(bcast16<10>(gv), bcast16<11>(gv), bcast16<12>(gv));

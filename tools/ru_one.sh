@@ -1,6 +1,7 @@
 #!/bin/bash
 # Register / scratch report of ONE step kernel instantiation (a few seconds to a minute instead of
 # the whole library's four): tools/ru_one.sh "step_kernel_o2<1, 0, 1, 1, 2>" [extra hipcc flags]
+# (an object or ReachAO kernel as its unit builds it: add -DPGX_CONTACT_INPLACE=1; an arm kernel: SLP=" ")
 set -e
 K=${1:-"step_kernel_o2<1, 0, 1, 1, 2>"}
 shift || true
