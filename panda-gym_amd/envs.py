@@ -253,10 +253,17 @@ class PandaVecEnv(_VecEnvBase):
                  n_substeps: int = 20, model_name: str = "panda_custom0", contacts: bool = True,
                  lanes_per_env: int = 0, full_manifold: Optional[bool] = None,
                  sim_params: Optional[Dict[str, Any]] = None, lib_path: Optional[str] = None,
-                 reset_rng: str = "philox", nonfinite: str = "off"):
+                 reset_rng: str = "philox", nonfinite: str = "off",
+                 joint_forces: Optional[Sequence[float]] = None):
         """``sim_params``: pgx_sim_params fields to override (the default library runs only the
         compiled parameters and refuses others; ``lib_path`` = libpgx_rtmodel.so reads them from
         the handle).
+
+        ``joint_forces``: pgx_config.joint_forces, the position motors' largest force per dof in
+        N m (default: the reference's, panda.py:63; at most abi.MAX_DOFS values, the arm's 7 first).
+        The motor row's impulse bound, joint_forces x dt, is part of the compiled constant block, so
+        like ``sim_params`` other values need ``lib_path`` = libpgx_rtmodel.so; all zeros is a limp
+        arm (the motor rows stay at zero impulse).
 
         ``nonfinite``: the per-env non-finite guard (pgx_config.nonfinite_guard).
         ``"off"`` (default): none -- an env whose state turns NaN / inf keeps writing NaN
@@ -295,6 +302,12 @@ class PandaVecEnv(_VecEnvBase):
         self._cfg = abi.make_config(self.spec, self.num_envs, self._model, self._params, seed=seed,
                                     env_id_offset=env_id_offset, contacts=contacts, lanes_per_env=lanes_per_env,
                                     full_manifold=full_manifold)
+        if joint_forces is not None:
+            forces = [float(f) for f in joint_forces]
+            if len(forces) > abi.MAX_DOFS or not all(np.isfinite(f) and f >= 0.0 for f in forces):
+                raise ValueError(f"joint_forces: at most {abi.MAX_DOFS} finite values >= 0, got {forces}")
+            for d, f in enumerate(forces):
+                self._cfg.joint_forces[d] = f
         if self.spec.task == abi.TASK_REACH_AO:
             # the reset sampler's EE centre and its capsules at the neutral pose, fp64 (pgx.h
             # ao_ee_neutral, ao_capsules_neutral): the device's accept / reject tests run on these values

@@ -125,6 +125,26 @@ def test_compiled_default_model_is_current():
         lib.pgx_destroy(h)
 
 
+def test_default_library_refuses_other_joint_forces():
+    """pgx_config.joint_forces (PandaVecEnv(joint_forces=...)) reaches the constant block as the
+    motor rows' impulse bound, joint_forces x dt: the default library refuses other values before
+    any HIP call and names the block's word, as for every other compiled parameter."""
+    from panda_gym_amd import _native
+
+    lib = _native.load()
+    h = C.c_void_p()
+    words = []
+    for d, f in ((0, 0.0), (6, 6.0)):   # a limp first joint; another force on the last arm joint
+        cfg = abi.make_config(abi.EnvSpec(), 8, abi.make_model(load_model("panda_custom0")), abi.default_sim_params())
+        assert cfg.joint_forces[d] == abi.JOINT_FORCES[d] != f
+        cfg.joint_forces[d] = f
+        assert lib.pgx_create(C.byref(cfg), 0, C.byref(h)) == abi.PGX_E_UNSUPPORTED
+        msg = lib.pgx_last_error().decode()
+        assert "compiled for" in msg
+        words.append(int(re.search(r"constant block word (\d+)", msg).group(1)))
+    assert words[1] == words[0] + 6, words   # max_impulse[0], max_impulse[6]
+
+
 def test_constants_match_header():
     hdr = open(os.path.join(ROOT, "include", "pgx.h")).read()
 
