@@ -503,12 +503,100 @@ int pgx_replay_row_stride(const pgx_replay_config* cfg);
 int pgx_replay_create(const pgx_replay_config* cfg, int device, pgx_replay_handle* out);
 void pgx_replay_destroy(pgx_replay_handle h);
 int pgx_replay_add(pgx_replay_handle h, const pgx_transition* t, void* stream);
-/* Number of transitions added per env so far (host-side counter, no sync). */
+/* Number of transitions added per env so far: the host mirror of the device word `added` (below),
+ * no sync.  The mirror counts the add / collect calls the host made, so it is exact while every
+ * add ran as a direct call; it is stale once a captured add or collect has been replayed (a replay
+ * advances the device word only) or a collect without a carry was refused on the device, until
+ * pgx_replay_state refreshes it. */
 int64_t pgx_replay_size(pgx_replay_handle h);
 int pgx_replay_sample(pgx_replay_handle h, int64_t batch, uint64_t draw, pgx_replay_batch* out, void* stream);
 /* Device views of the bookkeeping arrays [capacity][n_envs] i32 and of the number of valid
  * transitions after the last add() (i32 scalar), for tests / checkpoint / the host guard. */
 int pgx_replay_episode_arrays(pgx_replay_handle h, int32_t** ep_start, int32_t** ep_length, int32_t** n_valid);
+
+/* Collection on the device.  The ring position is a device word: `added`, the adds and collects
+ * stored so far (int64), pos = added % capacity.  Every kernel reads it from there (pgx_replay_add
+ * too), and the single-workgroup scan that runs behind every add and collect advances it, so a
+ * captured add or collect lands in the next slot on every replay.  Beside it live a sticky errors
+ * word (PGX_REPLAY_ERR_*), the flag "carry set", and the carry: SB3's _last_original_obs, per env
+ * carry_stride = round_up(obs_dim + 6, 4) floats laid out as the head of a record,
+ *   obs[obs_dim] | achieved_goal[3] | desired_goal[3] | zero padding.
+ *
+ * set_last / collect / truncate_last_trajectory enqueue kernels on `stream` and nothing else: no
+ * memcpy or memset node, no allocation, no synchronisation, so they capture into a hipGraph behind
+ * pgx_step.
+ *
+ * collect, per env (SB3 OffPolicyAlgorithm._store_transition over the auto-resetting VecEnv):
+ *   done    = terminated | truncated
+ *   timeout = handle_timeout ? truncated & ~terminated : 0
+ *   next_*  = done ? terminal_* : the post-step obs / achieved_goal / desired_goal
+ *   record  = carry obs | ag | dg | action | reward | next_obs | next_ag | next_dg |
+ *             done * (1 - timeout) | ep_start | ep_length, stored at pos with pgx_replay_add's
+ *             bookkeeping (the overwritten episode invalidated, ep_start, the episode length
+ *             written over the episode of a done env, whose next episode starts at pos + 1)
+ *   carry   = the post-step observation (of a done env: the first one of its new episode)
+ * then the valid list is refreshed and added += 1.  Without a carry (no set_last yet) nothing is
+ * stored, added stays, and PGX_REPLAY_ERR_NO_CARRY is set.
+ *
+ * truncate_last_trajectory closes every open episode where it stands, SB3's
+ * HerReplayBuffer.truncate_last_trajectory (after a forced reset, an env switch or the end of
+ * learn()); for every env with cur_ep_start != pos:
+ *   the episode [cur_ep_start, pos) (unwrapped by + capacity) gets its length, in ep_length and in
+ *   the records' copies; cur_ep_start = pos;
+ *   SB3 sets dones[pos - 1] = True and, with handle_timeout_termination, timeouts[pos - 1] = True:
+ *   the stored done * (1 - timeout) of the transition at pos - 1 (capacity - 1 for pos = 0) becomes
+ *   1 when handle_timeout is 0 and stays 0 when it is 1;
+ * then the valid list is refreshed.  An env at an episode start is left alone, so a second call
+ * changes nothing.  The carry stays: set it for the observation the next collect starts from. */
+#define PGX_REPLAY_ERR_NO_CARRY 1   /* pgx_replay_collect before pgx_replay_set_last: nothing stored */
+
+/* Device pointers of one collect: the step's action, then the env's step outputs (pgx_step_out's
+ * buffers).  Nothing is written. */
+typedef struct pgx_replay_step {
+    const float* action;                  /* [N,action_dim] */
+    const float* reward;                  /* [N] */
+    const uint8_t* terminated;            /* [N] */
+    const uint8_t* truncated;             /* [N] */
+    const float* obs;                     /* [N,obs_dim] post-step observation (the next carry) */
+    const float* achieved_goal;           /* [N,3] */
+    const float* desired_goal;            /* [N,3] */
+    const float* terminal_obs;            /* [N,obs_dim] read where terminated | truncated */
+    const float* terminal_achieved_goal;  /* [N,3] */
+    const float* terminal_desired_goal;   /* [N,3] */
+    int32_t handle_timeout;               /* SB3 handle_timeout_termination */
+    int32_t pad0;
+} pgx_replay_step;
+
+/* Device views of everything stored, for tests and a checkpoint: records
+ * [capacity][n_envs][record_stride], the carry [n_envs][carry_stride], ep_start / ep_length
+ * [capacity][n_envs], cur_ep_start [n_envs], the words. */
+typedef struct pgx_replay_views {
+    float* records;
+    float* carry;
+    int32_t* ep_start;
+    int32_t* ep_length;
+    int32_t* cur_ep_start;
+    int32_t* n_valid;
+    int64_t* added;
+    uint32_t* errors;
+    int32_t* carry_set;
+    int32_t record_stride;
+    int32_t carry_stride;
+} pgx_replay_views;
+
+/* The carry: obs [N,obs_dim], achieved_goal / desired_goal [N,3] f32 (the observation of
+ * env.reset()); sets the flag "carry set".  One launch. */
+int pgx_replay_set_last(pgx_replay_handle h, const float* obs, const float* achieved_goal, const float* desired_goal,
+                        void* stream);
+/* One collect launch in front of pgx_replay_add's count / scan / scatter. */
+int pgx_replay_collect(pgx_replay_handle h, const pgx_replay_step* io, void* stream);
+/* One launch, then count / scan / scatter. */
+int pgx_replay_truncate_last_trajectory(pgx_replay_handle h, int32_t handle_timeout, void* stream);
+/* added, n_valid and errors after synchronising `stream` (each may be NULL); refreshes the host
+ * mirror of pgx_replay_size; clear != 0 zeroes errors. */
+int pgx_replay_state(pgx_replay_handle h, int64_t* added, int32_t* n_valid, uint32_t* errors, int32_t clear,
+                     void* stream);
+int pgx_replay_arrays(pgx_replay_handle h, pgx_replay_views* out);
 
 /* ------------------------------------------------------------------------
  * VecNormalize: the observation / reward normalisation the reference's training

@@ -10,8 +10,8 @@ import os
 
 from .abi import PGX_E_INVALID  # noqa: F401 (re-exported for the C-ABI tests)
 from .abi import (PgxConfig, PgxMonitorConfig, PgxMonitorIo, PgxMonitorTotals, PgxNormConfig, PgxNormIo, PgxReplayBatch,
-                  PgxReplayConfig, PgxRolloutBatch, PgxRolloutConfig, PgxRolloutIo, PgxRolloutViews, PgxStateView, PgxStepOut,
-                  PgxTransition)
+                  PgxReplayConfig, PgxReplayStep, PgxReplayViews, PgxRolloutBatch, PgxRolloutConfig, PgxRolloutIo,
+                  PgxRolloutViews, PgxStateView, PgxStepOut, PgxTransition)
 
 LIB_PATH = os.environ.get("PGX_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpgx.so")
 
@@ -22,6 +22,8 @@ EXPORTS = [
     "pgx_set_rng_streams", "pgx_get_rng_streams",
     "pgx_replay_create", "pgx_replay_destroy", "pgx_replay_add", "pgx_replay_size", "pgx_replay_sample",
     "pgx_replay_episode_arrays", "pgx_replay_row_dim", "pgx_replay_row_stride",
+    "pgx_replay_set_last", "pgx_replay_collect", "pgx_replay_truncate_last_trajectory", "pgx_replay_state",
+    "pgx_replay_arrays",
     "pgx_norm_create", "pgx_norm_destroy", "pgx_norm_step", "pgx_norm_reset", "pgx_norm_rows", "pgx_norm_apply",
     "pgx_norm_set_training", "pgx_norm_set_keys", "pgx_norm_get_stats", "pgx_norm_set_stats",
     "pgx_monitor_create", "pgx_monitor_destroy", "pgx_monitor_step", "pgx_monitor_reset", "pgx_monitor_clear",
@@ -87,6 +89,12 @@ def load(path: str = None):
     lib.pgx_replay_sample.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(PgxReplayBatch), C.c_void_p]
     lib.pgx_replay_episode_arrays.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_void_p)]
+    lib.pgx_replay_set_last.argtypes = [C.c_void_p] * 5
+    lib.pgx_replay_collect.argtypes = [C.c_void_p, C.POINTER(PgxReplayStep), C.c_void_p]
+    lib.pgx_replay_truncate_last_trajectory.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.pgx_replay_state.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
+                                     C.c_int32, C.c_void_p]
+    lib.pgx_replay_arrays.argtypes = [C.c_void_p, C.POINTER(PgxReplayViews)]
     lib.pgx_norm_create.argtypes = [C.POINTER(PgxNormConfig), C.c_int, C.POINTER(C.c_void_p)]
     lib.pgx_norm_destroy.argtypes = [C.c_void_p]
     lib.pgx_norm_destroy.restype = None

@@ -145,6 +145,28 @@ class PgxReplayBatch(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("slot", C.c_void_p), ("env", C.c_void_p), ("goal_slot", C.c_void_p)]
 
 
+# HER collection on the device (include/pgx.h, pgx_replay_collect): the bits of the sticky error word
+REPLAY_ERR_NO_CARRY = 1
+REPLAY_ERRORS = {REPLAY_ERR_NO_CARRY: "PGX_REPLAY_ERR_NO_CARRY: collect() before set_last() (nothing was stored)"}
+
+
+class PgxReplayStep(C.Structure):
+    _fields_ = [
+        ("action", C.c_void_p), ("reward", C.c_void_p), ("terminated", C.c_void_p), ("truncated", C.c_void_p),
+        ("obs", C.c_void_p), ("achieved_goal", C.c_void_p), ("desired_goal", C.c_void_p),
+        ("terminal_obs", C.c_void_p), ("terminal_achieved_goal", C.c_void_p), ("terminal_desired_goal", C.c_void_p),
+        ("handle_timeout", C.c_int32), ("pad0", C.c_int32),
+    ]
+
+
+class PgxReplayViews(C.Structure):
+    _fields_ = [
+        ("records", C.c_void_p), ("carry", C.c_void_p), ("ep_start", C.c_void_p), ("ep_length", C.c_void_p),
+        ("cur_ep_start", C.c_void_p), ("n_valid", C.c_void_p), ("added", C.c_void_p), ("errors", C.c_void_p),
+        ("carry_set", C.c_void_p), ("record_stride", C.c_int32), ("carry_stride", C.c_int32),
+    ]
+
+
 # VecNormalize (include/pgx.h, pgx_norm_*): key bits of PgxNormConfig.key_mask in the order of the
 # columns, and pgx_norm_apply's key for rewards
 NORM_KEYS = ("observation", "achieved_goal", "desired_goal")

@@ -15,6 +15,10 @@
  *             compute_reward(next_achieved_goal[t], goal) in float32
  *             (reach.py:84-89 on float32 arrays); dones = done * (1 - timeout);
  *             output rows real first, then virtual (SB3 concatenation order).
+ *   collect(): add() with the transition put together on the device from the carry (SB3's
+ *             _last_original_obs) and the env's step outputs, one launch (pgx.h, "Collection on
+ *             the device"); the ring position is a device word, so it captures into the step graph.
+ *   truncate_last_trajectory(): SB3's, closes the open episodes where they stand.
  * Draws: Philox4x32-10, key = buffer seed, counter = (sample lo, sample hi,
  * draw lo, TAG_HER ^ draw hi); u0 = top 53 bits of words 0-1 picks the
  * transition (floor(u0 * n_valid)), u1 of words 2-3 picks t'.
@@ -48,6 +52,17 @@ struct RingPtrs {
     float* rec;                 /* [C][N][R] */
     int32_t *ep_start, *ep_length, *cur_ep_start;
     int32_t *valid, *block_count, *n_valid;
+};
+
+/* What collection adds to the blob, in a struct of its own: the sampling kernels take RingPtrs
+ * alone, so their arguments are what they were. */
+struct RingCtl {
+    float* carry;               /* [N][W]: obs | achieved_goal | desired_goal | zero padding */
+    int64_t* added;             /* adds and collects stored so far; pos = added % C.  Written by
+                                 * scan_blocks_kernel alone */
+    uint32_t* errors;           /* sticky PGX_REPLAY_ERR_* */
+    int32_t* carry_set;
+    int32_t W, pad;             /* carry stride: round_up(obs_dim + 6, 4) */
 };
 
 /* field offsets inside a row / record (floats) */
@@ -99,11 +114,37 @@ __device__ __forceinline__ float record_value(const RingDims& d, const pgx_trans
     return 0.0f;
 }
 
-__global__ __launch_bounds__(64) void add_kernel(RingPtrs p, RingDims d, int32_t pos, pgx_transition t) {
+/* SB3's episode bookkeeping of one stored transition (one lane per env): env e's record at pos has
+ * been written, of the episode that started at cur; a done one ends it at `end` with length len */
+__device__ __forceinline__ void bookkeep(const RingPtrs& p, const RingDims& d, int e, int32_t pos, int32_t cur, bool dn,
+                                         int32_t end, int32_t len) {
+    const int N = d.n, C = d.cap;
+    const size_t se = (size_t)pos * N + e;
+    /* an old episode is being overwritten: its remaining transitions become invalid */
+    const int32_t old_len = p.ep_length[se];
+    if (old_len > 0) {
+        const int32_t old_end = p.ep_start[se] + old_len;
+        for (int32_t k = pos; k < old_end; k++) p.ep_length[(size_t)(k % C) * N + e] = 0;
+    }
+    p.ep_start[se] = cur;
+    if (dn) {  /* SB3 _compute_episode_length: the new episode spans [cur, end) */
+        for (int32_t k = cur; k < end; k++) {
+            const size_t sk = (size_t)(k % C) * N + e;
+            p.ep_length[sk] = len;
+            if (k % C != pos) p.rec[sk * d.R + d.epl] = ibits(len);  /* own record written by the caller */
+        }
+        p.cur_ep_start[e] = (pos + 1) % C;
+    }
+}
+
+/* pos comes from the device word: nothing in this launch writes it (scan_blocks_kernel, behind it
+ * in stream order, does) */
+__global__ __launch_bounds__(64) void add_kernel(RingPtrs p, RingDims d, RingCtl k, pgx_transition t) {
     const int g = threadIdx.x % GROUP;
     const int e = blockIdx.x * (64 / GROUP) + threadIdx.x / GROUP;
     const int N = d.n, C = d.cap;
     if (e >= N) return;
+    const int32_t pos = (int32_t)(*k.added % C);
     const size_t se = (size_t)pos * N + e;
     const int32_t cur = p.cur_ep_start[e];
     const bool dn = t.done[e] != 0;
@@ -122,22 +163,131 @@ __global__ __launch_bounds__(64) void add_kernel(RingPtrs p, RingDims d, int32_t
         v.w = record_value(d, t, e, 4 * c + 3, dones, cur, len);
         *reinterpret_cast<float4*>(rec + 4 * c) = v;
     }
-    if (g != 0) return;
-    /* an old episode is being overwritten: its remaining transitions become invalid */
-    const int32_t old_len = p.ep_length[se];
-    if (old_len > 0) {
-        const int32_t old_end = p.ep_start[se] + old_len;
-        for (int32_t k = pos; k < old_end; k++) p.ep_length[(size_t)(k % C) * N + e] = 0;
+    if (g == 0) bookkeep(p, d, e, pos, cur, dn, end, len);
+}
+
+/* -------------------------------------------------------------- collect */
+/* record float f >= act of env e: the action, the reward, the next observation (the terminal one of
+ * a done env), the stored done, the episode fields */
+__device__ __forceinline__ float step_value(const RingDims& d, const pgx_replay_step& io, int e, int f, bool dn,
+                                            float dones, int32_t cur, int32_t len) {
+    if (f < d.rew) return io.action[(size_t)e * d.ad + (f - d.act)];
+    if (f == d.rew) return io.reward[e];
+    if (f < d.nag) return (dn ? io.terminal_obs : io.obs)[(size_t)e * d.od + (f - d.nobs)];
+    if (f < d.ndg) return (dn ? io.terminal_achieved_goal : io.achieved_goal)[(size_t)e * 3 + (f - d.nag)];
+    if (f < d.done) return (dn ? io.terminal_desired_goal : io.desired_goal)[(size_t)e * 3 + (f - d.ndg)];
+    if (f == d.done) return dones;
+    if (f == d.eps) return ibits(cur);
+    if (f == d.epl) return ibits(len);
+    return 0.0f;
+}
+
+/* float f < act of the post-step observation dict, as the carry holds it */
+__device__ __forceinline__ float carry_value(const RingDims& d, const pgx_replay_step& io, int e, int f) {
+    if (f < d.ag) return io.obs[(size_t)e * d.od + f];
+    if (f < d.dg) return io.achieved_goal[(size_t)e * 3 + (f - d.ag)];
+    return io.desired_goal[(size_t)e * 3 + (f - d.dg)];
+}
+
+/* add_kernel's geometry.  The transition is put together from the carry and the env's step outputs
+ * where they lie; the lane that reads four carry floats is the one that overwrites them with the
+ * post-step observation, so nothing is ordered between lanes.  Without a carry: the error bit and
+ * nothing else (scan_blocks_kernel then leaves `added` alone). */
+__global__ __launch_bounds__(64) void collect_kernel(RingPtrs p, RingDims d, RingCtl k, pgx_replay_step io) {
+    const int g = threadIdx.x % GROUP;
+    const int e = blockIdx.x * (64 / GROUP) + threadIdx.x / GROUP;
+    const int N = d.n, C = d.cap;
+    if (*k.carry_set == 0) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(k.errors, (uint32_t)PGX_REPLAY_ERR_NO_CARRY);
+        return;
     }
-    p.ep_start[se] = cur;
-    if (dn) {  /* SB3 _compute_episode_length: the new episode spans [cur, end) */
-        for (int32_t k = cur; k < end; k++) {
-            const size_t sk = (size_t)(k % C) * N + e;
-            p.ep_length[sk] = len;
-            if (k % C != pos) p.rec[sk * d.R + d.epl] = ibits(len);  /* own record written above */
+    if (e >= N) return;
+    const int32_t pos = (int32_t)(*k.added % C);
+    const size_t se = (size_t)pos * N + e;
+    const int32_t cur = p.cur_ep_start[e];
+    const bool te = io.terminated[e] != 0, tr = io.truncated[e] != 0;
+    const bool dn = te || tr;
+    const bool to = io.handle_timeout != 0 && tr && !te;
+    int32_t end = (pos + 1) % C;
+    if (end < cur) end += C;
+    const int32_t len = dn ? end - cur : 0;
+    const float dones = (float)dn * (1.0f - (float)to);
+    float* rec = p.rec + se * d.R;
+    float* car = k.carry + (size_t)e * k.W;
+    for (int c = g; 4 * c < d.R; c += GROUP) {
+        float vv[4];
+        if (4 * c < d.act) {   /* 4 c + 3 < W: the carry's padding is zero and replaced below */
+            const float4 cv = *reinterpret_cast<const float4*>(car + 4 * c);
+            vv[0] = cv.x; vv[1] = cv.y; vv[2] = cv.z; vv[3] = cv.w;
+            float nc[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) nc[u] = 4 * c + u < d.act ? carry_value(d, io, e, 4 * c + u) : 0.0f;
+            *reinterpret_cast<float4*>(car + 4 * c) = make_float4(nc[0], nc[1], nc[2], nc[3]);
         }
-        p.cur_ep_start[e] = (pos + 1) % C;
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+            if (4 * c + u >= d.act) vv[u] = step_value(d, io, e, 4 * c + u, dn, dones, cur, len);
+        *reinterpret_cast<float4*>(rec + 4 * c) = make_float4(vv[0], vv[1], vv[2], vv[3]);
     }
+    /* bookkeep()'s stores, its two loops dealt over the group's 16 lanes (an env that ends a
+     * 50-step episode has 100 scattered stores to make, and about N / 50 envs do every step): lane 0
+     * reads what slot pos held and alone writes that slot's words; the loops leave slot pos out.
+     * The two ranges share no other slot: an old episode that reached into [cur, pos) was
+     * invalidated, up to its end, by the add that wrote there. */
+    int32_t old_len = 0, old_start = 0;
+    if (g == 0) {
+        old_len = p.ep_length[se];
+        old_start = p.ep_start[se];
+    }
+    old_len = __shfl(old_len, 0, GROUP);
+    old_start = __shfl(old_start, 0, GROUP);
+    if (old_len > 0)
+        for (int32_t s = pos + 1 + g; s < old_start + old_len; s += GROUP) p.ep_length[(size_t)(s % C) * N + e] = 0;
+    if (dn)
+        for (int32_t s = cur + g; s < end; s += GROUP) {
+            if (s % C == pos) continue;
+            const size_t sk = (size_t)(s % C) * N + e;
+            p.ep_length[sk] = len;
+            p.rec[sk * d.R + d.epl] = ibits(len);
+        }
+    if (g == 0) {
+        p.ep_start[se] = cur;
+        p.ep_length[se] = len;   /* 0 while the episode is open */
+        if (dn) p.cur_ep_start[e] = (pos + 1) % C;
+    }
+}
+
+__global__ __launch_bounds__(256) void set_last_kernel(RingDims d, RingCtl k, const float* obs, const float* ag,
+                                                       const float* dg) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *k.carry_set = 1;
+    if (i >= (int64_t)d.n * k.W) return;
+    const int e = (int)(i / k.W), f = (int)(i % k.W);
+    float v = 0.0f;
+    if (f < d.ag) v = obs[(size_t)e * d.od + f];
+    else if (f < d.dg) v = ag[(size_t)e * 3 + (f - d.ag)];
+    else if (f < d.act) v = dg[(size_t)e * 3 + (f - d.dg)];
+    k.carry[i] = v;
+}
+
+/* SB3 truncate_last_trajectory, one lane per env (the episodes of two envs share nothing) */
+__global__ __launch_bounds__(64) void truncate_kernel(RingPtrs p, RingDims d, RingCtl k, int32_t handle_timeout) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    const int N = d.n, C = d.cap;
+    if (e >= N) return;
+    const int32_t pos = (int32_t)(*k.added % C);
+    const int32_t cur = p.cur_ep_start[e];
+    if (cur == pos) return;
+    int32_t end = pos;
+    if (end < cur) end += C;
+    const int32_t len = end - cur;
+    for (int32_t s = cur; s < end; s++) {
+        const size_t sk = (size_t)(s % C) * N + e;
+        p.ep_length[sk] = len;
+        p.rec[sk * d.R + d.epl] = ibits(len);
+    }
+    p.cur_ep_start[e] = pos;
+    if (!handle_timeout) p.rec[((size_t)((pos + C - 1) % C) * N + e) * d.R + d.done] = 1.0f;
 }
 
 /* ------------------------------------------- ordered compaction of ep_length > 0 */
@@ -157,8 +307,13 @@ __global__ __launch_bounds__(SCAN_BLOCK) void count_kernel(RingPtrs p, int64_t t
     }
 }
 
-/* exclusive scan of the block counts in one workgroup (block_count -> offsets, n_valid) */
-__global__ __launch_bounds__(1024) void scan_blocks_kernel(RingPtrs p, int32_t nblocks) {
+/* what scan_blocks_kernel does to `added` */
+enum { ADV_NONE = 0, ADV_ADD = 1, ADV_COLLECT = 2 };   /* truncate; add; collect: only with a carry */
+
+/* exclusive scan of the block counts in one workgroup (block_count -> offsets, n_valid).  It runs
+ * behind every add and collect in stream order and is the one writer of `added`: the kernel in
+ * front of it has read the word in all its workgroups, the next one reads it after this. */
+__global__ __launch_bounds__(1024) void scan_blocks_kernel(RingPtrs p, int32_t nblocks, RingCtl k, int32_t advance) {
     __shared__ int32_t s[1024];
     int32_t carry = 0;
     for (int32_t base = 0; base < nblocks; base += 1024) {
@@ -176,7 +331,10 @@ __global__ __launch_bounds__(1024) void scan_blocks_kernel(RingPtrs p, int32_t n
         carry += s[1023];
         __syncthreads();
     }
-    if (threadIdx.x == 0) *p.n_valid = carry;
+    if (threadIdx.x == 0) {
+        *p.n_valid = carry;
+        if (advance == ADV_ADD || (advance == ADV_COLLECT && *k.carry_set != 0)) *k.added += 1;
+    }
 }
 
 __global__ __launch_bounds__(SCAN_BLOCK) void scatter_kernel(RingPtrs p, int64_t total) {
@@ -431,10 +589,25 @@ struct pgx_replay {
     pgx_replay_config cfg;
     RingPtrs p;
     RingDims d;
+    RingCtl k;
     void* blob;
-    int32_t pos;
+    /* host mirror of the device words: the calls the host made (pgx.h, pgx_replay_size) */
     int64_t added;
+    bool carry_set;
 };
+
+namespace {
+
+/* refresh of the valid list behind an add / collect / truncate, and the advance of `added` */
+void launch_compaction(pgx_replay* h, hipStream_t st, int32_t advance) {
+    const int64_t total = (int64_t)h->d.n * h->d.cap;
+    const int32_t nblocks = (int32_t)((total + SCAN_BLOCK - 1) / SCAN_BLOCK);
+    hipLaunchKernelGGL(count_kernel, dim3(nblocks), dim3(SCAN_BLOCK), 0, st, h->p, total);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, h->p, nblocks, h->k, advance);
+    hipLaunchKernelGGL(scatter_kernel, dim3(nblocks), dim3(SCAN_BLOCK), 0, st, h->p, total);
+}
+
+}  // namespace
 
 int pgx_set_error(int code, const char* msg);  /* pgx_api.cpp: sets pgx_last_error() */
 
@@ -471,9 +644,11 @@ int pgx_replay_create(const pgx_replay_config* cfg, int device, pgx_replay_handl
     const size_t N = cfg->n_envs, C = cfg->capacity, T = N * C;
     const size_t nblocks = (T + SCAN_BLOCK - 1) / SCAN_BLOCK;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t sizes[] = {T * h->d.R * 4, T * 4, T * 4, N * 4, T * 4, nblocks * 4, 4};
-    size_t off[7], total = 0;
-    for (int i = 0; i < 7; i++) { off[i] = total; total = al(total + sizes[i]); }
+    const size_t W = ((size_t)h->d.act + 3) & ~(size_t)3;   /* carry stride */
+    /* ..., the carry [N][W], the words: added (i64) | errors | carry_set */
+    const size_t sizes[] = {T * h->d.R * 4, T * 4, T * 4, N * 4, T * 4, nblocks * 4, 4, N * W * 4, 16};
+    size_t off[9], total = 0;
+    for (int i = 0; i < 9; i++) { off[i] = total; total = al(total + sizes[i]); }
     if (hipMalloc(&h->blob, total) != hipSuccess) {
         delete h;
         return pgx_set_error(PGX_E_NOMEM, "pgx_replay_create: hipMalloc failed");
@@ -492,8 +667,15 @@ int pgx_replay_create(const pgx_replay_config* cfg, int device, pgx_replay_handl
     p.valid = (int32_t*)(b + off[4]);
     p.block_count = (int32_t*)(b + off[5]);
     p.n_valid = (int32_t*)(b + off[6]);
-    h->pos = 0;
+    RingCtl& k = h->k;
+    k.carry = (float*)(b + off[7]);
+    k.added = (int64_t*)(b + off[8]);
+    k.errors = (uint32_t*)(b + off[8] + 8);
+    k.carry_set = (int32_t*)(b + off[8] + 12);
+    k.W = (int32_t)W;
+    k.pad = 0;
     h->added = 0;
+    h->carry_set = false;
     *out = h;
     return PGX_OK;
 }
@@ -512,15 +694,86 @@ int pgx_replay_add(pgx_replay_handle h, const pgx_transition* t, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const int N = h->d.n;
     const int per_block = 64 / GROUP;
-    hipLaunchKernelGGL(add_kernel, dim3((N + per_block - 1) / per_block), dim3(64), 0, st, h->p, h->d, h->pos, *t);
-    const int64_t total = (int64_t)h->d.n * h->d.cap;
-    const int32_t nblocks = (int32_t)((total + SCAN_BLOCK - 1) / SCAN_BLOCK);
-    hipLaunchKernelGGL(count_kernel, dim3(nblocks), dim3(SCAN_BLOCK), 0, st, h->p, total);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, h->p, nblocks);
-    hipLaunchKernelGGL(scatter_kernel, dim3(nblocks), dim3(SCAN_BLOCK), 0, st, h->p, total);
+    hipLaunchKernelGGL(add_kernel, dim3((N + per_block - 1) / per_block), dim3(64), 0, st, h->p, h->d, h->k, *t);
+    launch_compaction(h, st, ADV_ADD);
     if (hipGetLastError() != hipSuccess) return pgx_set_error(PGX_E_HIP, "pgx_replay_add: launch failed");
-    h->pos = (h->pos + 1) % h->d.cap;
     h->added += 1;
+    return PGX_OK;
+}
+
+int pgx_replay_set_last(pgx_replay_handle h, const float* obs, const float* achieved_goal, const float* desired_goal,
+                        void* stream) {
+    if (!h || !obs || !achieved_goal || !desired_goal)
+        return pgx_set_error(PGX_E_INVALID, "pgx_replay_set_last: null handle or observation pointer");
+    const int64_t n = (int64_t)h->d.n * h->k.W;
+    hipLaunchKernelGGL(set_last_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->d, h->k,
+                       obs, achieved_goal, desired_goal);
+    if (hipGetLastError() != hipSuccess) return pgx_set_error(PGX_E_HIP, "pgx_replay_set_last: launch failed");
+    h->carry_set = true;
+    return PGX_OK;
+}
+
+int pgx_replay_collect(pgx_replay_handle h, const pgx_replay_step* io, void* stream) {
+    if (!h || !io || !io->action || !io->reward || !io->terminated || !io->truncated || !io->obs ||
+        !io->achieved_goal || !io->desired_goal || !io->terminal_obs || !io->terminal_achieved_goal ||
+        !io->terminal_desired_goal)
+        return pgx_set_error(PGX_E_INVALID, "pgx_replay_collect: null handle or step pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const int N = h->d.n;
+    const int per_block = 64 / GROUP;
+    hipLaunchKernelGGL(collect_kernel, dim3((N + per_block - 1) / per_block), dim3(64), 0, st, h->p, h->d, h->k, *io);
+    launch_compaction(h, st, ADV_COLLECT);
+    if (hipGetLastError() != hipSuccess) return pgx_set_error(PGX_E_HIP, "pgx_replay_collect: launch failed");
+    if (h->carry_set) h->added += 1;
+    return PGX_OK;
+}
+
+int pgx_replay_truncate_last_trajectory(pgx_replay_handle h, int32_t handle_timeout, void* stream) {
+    if (!h) return pgx_set_error(PGX_E_INVALID, "pgx_replay_truncate_last_trajectory: null handle");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(truncate_kernel, dim3((h->d.n + 63) / 64), dim3(64), 0, st, h->p, h->d, h->k, handle_timeout);
+    launch_compaction(h, st, ADV_NONE);
+    return hipGetLastError() == hipSuccess
+               ? PGX_OK
+               : pgx_set_error(PGX_E_HIP, "pgx_replay_truncate_last_trajectory: launch failed");
+}
+
+int pgx_replay_state(pgx_replay_handle h, int64_t* added, int32_t* n_valid, uint32_t* errors, int32_t clear,
+                     void* stream) {
+    if (!h) return pgx_set_error(PGX_E_INVALID, "pgx_replay_state: null handle");
+    const char* what = "pgx_replay_state: device read failed";
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return pgx_set_error(PGX_E_HIP, what);
+    struct { int64_t added; uint32_t errors; int32_t carry_set; } w = {0, 0u, 0};
+    int32_t nv = 0;
+    if (hipMemcpy(&w, h->k.added, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&nv, h->p.n_valid, sizeof(nv), hipMemcpyDeviceToHost) != hipSuccess)
+        return pgx_set_error(PGX_E_HIP, what);
+    h->added = w.added;
+    h->carry_set = w.carry_set != 0;
+    if (added) *added = w.added;
+    if (n_valid) *n_valid = nv;
+    if (errors) *errors = w.errors;
+    if (clear && w.errors != 0u) {
+        const uint32_t zero = 0u;
+        if (hipMemcpy(h->k.errors, &zero, sizeof(zero), hipMemcpyHostToDevice) != hipSuccess)
+            return pgx_set_error(PGX_E_HIP, what);
+    }
+    return PGX_OK;
+}
+
+int pgx_replay_arrays(pgx_replay_handle h, pgx_replay_views* out) {
+    if (!h || !out) return pgx_set_error(PGX_E_INVALID, "pgx_replay_arrays: null handle or views pointer");
+    out->records = h->p.rec;
+    out->carry = h->k.carry;
+    out->ep_start = h->p.ep_start;
+    out->ep_length = h->p.ep_length;
+    out->cur_ep_start = h->p.cur_ep_start;
+    out->n_valid = h->p.n_valid;
+    out->added = h->k.added;
+    out->errors = h->k.errors;
+    out->carry_set = h->k.carry_set;
+    out->record_stride = h->d.R;
+    out->carry_stride = h->k.W;
     return PGX_OK;
 }
 

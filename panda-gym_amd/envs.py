@@ -765,7 +765,7 @@ _INFO_TEMPLATES = [{"is_success": s, "is_truncated": c} for c in (False, True) f
 
 def _view(addr: int, shape, dtype, device):
     """Wrap a libpgx-owned device buffer as a torch tensor (no copy)."""
-    typestr = {torch.float32: "<f4", torch.float64: "<f8", torch.int32: "<i4"}[dtype]
+    typestr = {torch.float32: "<f4", torch.float64: "<f8", torch.int32: "<i4", torch.int64: "<i8"}[dtype]
 
     class _Iface:  # torch has no public from-pointer constructor; use __cuda_array_interface__
         __cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(addr), False),

@@ -11,6 +11,13 @@ views -- plus a device-resident path (``add_tensors``, ``add_from_vec_env``)
 that never leaves HBM.  Storage, episode bookkeeping, relabelling and reward
 recomputation run in libpgx.so (pgx_her.hip); there is no CPU fallback.
 
+Collection on the device: ``set_last(obs)`` keeps SB3's ``_last_original_obs`` as a
+device carry, ``collect_from_vec_env(venv, action)`` builds the transition from it and
+the env's own output buffers in one launch, the ring position is a device word (``pos``,
+``full`` and ``size()`` read it: one sync), so ``after_step(venv, actions)`` puts the
+collect into ``capture_steps``' graph, and ``truncate_last_trajectory()`` closes the open
+episodes after a forced reset (include/pgx.h, "Collection on the device").
+
 Draws: the device Philox stream (key = buffer seed, counter = (sample, call))
 replaces numpy's global RNG, so a sample is a pure function of (seed, call
 index, buffer contents) -- the oracle (oracle/her.py) reproduces it exactly.
@@ -146,17 +153,61 @@ class HerReplayBuffer:
     def ep_length(self) -> "torch.Tensor":
         return self._arrays()[1]
 
+    def _state(self, clear: bool = False):
+        """(added, n_valid, errors) from the device words: one sync; refreshes libpgx's host mirror."""
+        added, nv, err = C.c_int64(0), C.c_int32(0), C.c_uint32(0)
+        check(self.lib.pgx_replay_state(self._h, C.byref(added), C.byref(nv), C.byref(err), 1 if clear else 0,
+                                        self._stream()), "pgx_replay_state")
+        return int(added.value), int(nv.value), int(err.value)
+
     @property
     def pos(self) -> int:
-        return int(self.lib.pgx_replay_size(self._h) % self.buffer_size)
+        """The slot the next add or collect writes (a device word: this synchronises)."""
+        return self._state()[0] % self.buffer_size
 
     @property
     def full(self) -> bool:
-        return self.lib.pgx_replay_size(self._h) >= self.buffer_size
+        return self._state()[0] >= self.buffer_size
 
     def size(self) -> int:
         """SB3 BaseBuffer.size: transitions stored per env."""
-        return self.buffer_size if self.full else self.pos
+        return min(self._state()[0], self.buffer_size)
+
+    def raise_device_errors(self) -> None:
+        """Raise what the kernels flagged in the sticky device word and clear it (one sync)."""
+        err = self._state(clear=True)[2]
+        if err:
+            names = [msg for bit, msg in abi.REPLAY_ERRORS.items() if err & bit]
+            raise PgxError("; ".join(names) if names else f"replay device error flags 0x{err:x}")
+
+    def arrays(self) -> Dict[str, "torch.Tensor"]:
+        """Device views of everything stored: ``records`` [C, N, record_stride] and the fields as
+        strided views into it (``obs`` ... ``done`` as in a batch row, then ``rec_ep_start`` /
+        ``rec_ep_length``, the records' int32 copies), the carry ``last_observation`` [N, obs_dim],
+        ``last_achieved_goal`` / ``last_desired_goal`` [N, 3] (views into ``carry`` [N,
+        carry_stride]), ``ep_start`` / ``ep_length`` [C, N], ``cur_ep_start`` [N] and the words
+        ``n_valid``, ``added`` (int64), ``errors``, ``carry_set`` [1]."""
+        from .envs import _view
+
+        v = abi.PgxReplayViews()
+        check(self.lib.pgx_replay_arrays(self._h, C.byref(v)), "pgx_replay_arrays")
+        Cn, N, od, R, W, dev = self.buffer_size, self.n_envs, self.obs_dim, int(v.record_stride), \
+            int(v.carry_stride), self.device
+        rec = _view(v.records, (Cn, N, R), torch.float32, dev)
+        out = {"records": rec}
+        for name, off, w in self._fields:
+            out[name] = rec[:, :, off] if name in ("reward", "done") else rec[:, :, off:off + w]
+        irec = _view(v.records, (Cn, N, R), torch.int32, dev)
+        out["rec_ep_start"], out["rec_ep_length"] = irec[:, :, self.row_dim], irec[:, :, self.row_dim + 1]
+        carry = _view(v.carry, (N, W), torch.float32, dev)
+        out.update(carry=carry, last_observation=carry[:, :od], last_achieved_goal=carry[:, od:od + 3],
+                   last_desired_goal=carry[:, od + 3:od + 6],
+                   ep_start=_view(v.ep_start, (Cn, N), torch.int32, dev),
+                   ep_length=_view(v.ep_length, (Cn, N), torch.int32, dev),
+                   cur_ep_start=_view(v.cur_ep_start, (N,), torch.int32, dev),
+                   n_valid=_view(v.n_valid, (1,), torch.int32, dev), added=_view(v.added, (1,), torch.int64, dev),
+                   errors=_view(v.errors, (1,), torch.int32, dev), carry_set=_view(v.carry_set, (1,), torch.int32, dev))
+        return out
 
     # ------------------------------------------------------------------ add
     def add_tensors(self, obs, achieved_goal, desired_goal, action, reward, next_obs, next_achieved_goal,
@@ -205,6 +256,99 @@ class HerReplayBuffer:
         timeout = (tr & ~te).to(torch.uint8)
         self.add_tensors(obs["observation"], obs["achieved_goal"], obs["desired_goal"], action, venv.reward,
                          next_o, next_ag, next_dg, done, timeout)
+
+    # -------------------------------------------------------------- collect
+    def set_last(self, obs: Dict[str, Any]) -> None:
+        """The carry, SB3's ``_last_original_obs``: the raw observation dict the next step's action
+        is taken from (``env.reset()``'s; behind a ``VecNormalize``, ``get_original_obs``).  One
+        launch.  Call it again after every forced reset, behind ``truncate_last_trajectory()``."""
+        N = self.n_envs
+        f = torch.float32
+        t = [self._dev(obs["observation"], (N, self.obs_dim), f), self._dev(obs["achieved_goal"], (N, 3), f),
+             self._dev(obs["desired_goal"], (N, 3), f)]
+        check(self.lib.pgx_replay_set_last(self._h, *[C.c_void_p(x.data_ptr()) for x in t], self._stream()),
+              "pgx_replay_set_last")
+        self._keep_last = t   # read by the queued launch
+
+    def _launch_collect(self, action, reward, terminated, truncated, obs, ag, dg, tobs, tag, tdg) -> None:
+        io = abi.PgxReplayStep(*[x.data_ptr() for x in (action, reward, terminated, truncated, obs, ag, dg, tobs, tag,
+                                                        tdg)], 1 if self.handle_timeout_termination else 0, 0)
+        check(self.lib.pgx_replay_collect(self._h, C.byref(io), self._stream()), "pgx_replay_collect")
+
+    def collect_tensors(self, action, reward, obs: Dict[str, Any], terminated, truncated,
+                        terminal_obs: Dict[str, Any]) -> None:
+        """Store the step from the carry to ``obs``: ``action`` [N, A], ``reward`` [N], the post-step
+        observation dict, the step's flags [N] and the terminal observation dict (read for the envs
+        with ``terminated | truncated``).  done = terminated | truncated, timeout = truncated &
+        ~terminated (with ``handle_timeout_termination``), next_obs = the terminal observation of a
+        done env; the carry becomes ``obs``.  Device f32 / u8 contiguous tensors are read in place."""
+        N, od, f, u8 = self.n_envs, self.obs_dim, torch.float32, torch.uint8
+        t = [self._dev(action, (N, self.action_dim), f), self._dev(reward, (N,), f), self._dev(terminated, (N,), u8),
+             self._dev(truncated, (N,), u8)]
+        for o in (obs, terminal_obs):
+            t += [self._dev(o["observation"], (N, od), f), self._dev(o["achieved_goal"], (N, 3), f),
+                  self._dev(o["desired_goal"], (N, 3), f)]
+        self._launch_collect(*t)
+        self._keep = t   # alive until the stream has consumed them
+
+    @staticmethod
+    def _base_env(venv):
+        """The innermost ``PandaVecEnv`` behind ``VecMonitor`` / ``VecNormalize``: its buffers hold the
+        raw step outputs, which SB3's off-policy path stores (``get_original_obs`` / ``_reward``)."""
+        v = venv
+        while hasattr(v, "venv"):
+            v = v.venv
+        return v
+
+    def _step_buffers(self, venv):
+        v = self._base_env(venv)
+        return (v.reward, v.terminated, v.truncated, v.obs, v.achieved_goal, v.desired_goal, v.terminal_obs,
+                v.terminal_ag, v.terminal_dg)
+
+    def collect_from_vec_env(self, venv, action: "torch.Tensor") -> None:
+        """Store the step ``venv.step_tensors(action)`` has just taken, from the carry: one collect
+        launch that reads the env's own output buffers in place (no clone, no temporary), then the
+        valid-list refresh.  ``venv`` may be the env, a ``VecNormalize`` or a ``VecMonitor``: the raw
+        values of the env underneath are stored, as ``add_from_vec_env`` stores them."""
+        a = action
+        if a.dtype != torch.float32 or a.device != self.device or not a.is_contiguous() \
+                or tuple(a.shape) != (self.n_envs, self.action_dim):
+            a = self._dev(a, (self.n_envs, self.action_dim), torch.float32)
+        self._launch_collect(a, *self._step_buffers(venv))
+        self._keep = [a]
+
+    def after_step(self, venv, actions: Optional["torch.Tensor"] = None):
+        """The callable for ``venv.capture_steps(k, actions, after_step=...)`` of the env or either
+        wrapper: its i-th call enqueues the collect of step i, reading ``actions[i]`` -- the static
+        contiguous f32 [k, N, A] device buffer the captured steps read -- or, with ``actions=None``,
+        the env's own action buffer, which the in-graph random policy fills before every step."""
+        base = self._base_env(venv)
+        bufs = self._step_buffers(venv)
+        if actions is not None:
+            if not torch.is_tensor(actions) or actions.dim() != 3 or \
+                    tuple(actions.shape[1:]) != (self.n_envs, self.action_dim) or actions.dtype != torch.float32 \
+                    or actions.device != self.device or not actions.is_contiguous():
+                raise ValueError(f"actions must be a contiguous f32 [k, {self.n_envs}, {self.action_dim}] tensor on "
+                                 f"{self.device}")
+        count = [0]
+
+        def enqueue() -> None:
+            i = count[0]
+            if actions is not None and i >= actions.shape[0]:
+                raise IndexError(f"after_step: more than the {actions.shape[0]} steps its buffer holds")
+            self._launch_collect(actions[i] if actions is not None else base._actions, *bufs)
+            count[0] = i + 1
+
+        self._keep_graph = actions
+        return enqueue
+
+    def truncate_last_trajectory(self) -> None:
+        """SB3 ``HerReplayBuffer.truncate_last_trajectory``: close every open episode where it
+        stands, so that its transitions become valid and no relabelled goal is drawn across it.
+        Call it after a forced ``reset_tensors()``, an env switch or the end of a ``learn()``, then
+        ``set_last(obs)``.  A no-op for envs at an episode start."""
+        check(self.lib.pgx_replay_truncate_last_trajectory(self._h, 1 if self.handle_timeout_termination else 0,
+                                                           self._stream()), "pgx_replay_truncate_last_trajectory")
 
     # --------------------------------------------------------------- sample
     def alloc_batch(self, batch_size: int, with_indices: bool = True) -> Dict[str, "torch.Tensor"]:
