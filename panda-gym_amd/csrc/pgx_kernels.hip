@@ -195,6 +195,15 @@ typedef float f2 __attribute__((ext_vector_type(2)));   /* packed fp32 pair (v_p
 #ifndef PGX_PK_AO
 #define PGX_PK_AO 2
 #endif
+/* Lane owners (wide layout, arm kernels): capsule c's end points formed on
+ * lane c, link-7 damping body b on lane NJ + b, instead of on all 16 lanes of the row.  The
+ * switches are for A/B builds: both on in the product. */
+#ifndef PGX_OWN_CAPS
+#define PGX_OWN_CAPS 1
+#endif
+#ifndef PGX_OWN_DAMP
+#define PGX_OWN_DAMP 1
+#endif
 /* {a, b} += {ca, cb} s as one v_pk_fma_f32: each half is the fused multiply-add of the scalar
  * form, bit for bit, in one issue instead of two (two of a PGS row's register updates) */
 __device__ __forceinline__ void pk_fma_acc(float& a, float& b, f2 cab, float s) {
@@ -921,7 +930,14 @@ struct ContactLdsT {
     float4 g1q[W == 64 ? CG : 1][3][6][W == 64 ? W : 1];
     int cnt[2][W];
     float cache[CACHE_N][W];      /* (feature id, normal impulse): CG object-scene slots, then robot slots */
-    float capA[PGX_NCAP][3][W], capB[PGX_NCAP][3][W];   /* capsule end points, world */
+    /* capsule end points, world -- or, in the wide layout's arm kernels, which form them in
+     * registers (cap_ends_own), lane c's capsule constants, written once per launch (CapRow) */
+    union alignas(16) {
+        struct {
+            float capA[PGX_NCAP][3][W], capB[PGX_NCAP][3][W];
+        };
+        float capk[W == 64 ? 1 : GW][12];
+    };
     /* ReachAO: obstacle centres, per collision link the closest distance and unit vector */
     float aoC[PGX_AO_OBSTACLES][3][W];
     float aoD[PGX_AO_LINKS][W], aoU[PGX_AO_LINKS][3][W];
@@ -1666,21 +1682,127 @@ __device__ __forceinline__ CapLane cap_lane() {
     return CapLane{r, (int)fl, (int)ns, (int)j, (int)sl};
 }
 
+/* ---- lane owners (wide layout, arm kernels): a table constant per lane, applied once.
+ * mulc's products with the constant a per-lane register: every product rounded on its own and
+ * summed left to right (the operands are calls, so nothing contracts -- as kmul's), i.e. the
+ * bits of mulc for that lane's column.  mulc drops a zero constant's product as -0.0f, the
+ * identity of +; here the constant is +0 and own_cols puts -1 in its column of the matrix, so
+ * the product is that same -0.0f. */
+__device__ __forceinline__ float pmul(float x, float k) { return x * k; }
+__device__ __forceinline__ V3 mull(const M3& A, const float* v) {
+    return v3(pmul(A.m[0], v[0]) + pmul(A.m[1], v[1]) + pmul(A.m[2], v[2]),
+              pmul(A.m[3], v[0]) + pmul(A.m[4], v[1]) + pmul(A.m[5], v[2]),
+              pmul(A.m[6], v[0]) + pmul(A.m[7], v[1]) + pmul(A.m[8], v[2]));
+}
+/* lanes of MASK (one bit per lane of the wave) take a */
+template <uint64_t MASK>
+__device__ __forceinline__ float mask_sel(float a, float other) {
+    float r;
+    asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(other), "v"(a), "s"(MASK));
+    return r;
+}
+/* the wave's lanes L0 + k (k < N, in every row) whose constant T[k][t] is zero */
+template <int N>
+constexpr uint64_t zero_lanes(const float (&T)[N][3], int t, int L0, int K0 = 0) {
+    uint64_t mk = 0;
+    for (int k = K0; k < N; k++)
+        if (T[k][t] == 0.0f) mk |= 0x0001000100010001ull << (L0 + k);
+    return mk;
+}
+template <uint64_t Z0, uint64_t Z1, uint64_t Z2>
+__device__ __forceinline__ void own_cols(M3& R) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        if constexpr (Z0 != 0) R.m[3 * r] = mask_sel<Z0>(-1.0f, R.m[3 * r]);
+        if constexpr (Z1 != 0) R.m[3 * r + 1] = mask_sel<Z1>(-1.0f, R.m[3 * r + 1]);
+        if constexpr (Z2 != 0) R.m[3 * r + 2] = mask_sel<Z2>(-1.0f, R.m[3 * r + 2]);
+    }
+}
+/* capsule c's end points in its joint's frame on lane c (1 <= c < PGX_NCAP; 0 elsewhere: the base
+ * capsule hangs on no joint), selected from compile-time values like cap_lane()'s */
+struct CapEnds {
+    float a[3], b[3];
+};
+__device__ __forceinline__ CapEnds cap_ends_lane() {
+    CapEnds k = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
+    sfor<1, PGX_NCAP>([&](auto kc) __attribute__((always_inline)) {
+        constexpr int K = decltype(kc)::value;
+        static_assert(kCapJ[K] >= 0 && kCapJ[K] < NJ, "lane kCapJ[c] of the row holds capsule c's frame");
+#pragma unroll
+        for (int t = 0; t < 3; t++) {
+            if (kCapA[K][t] != 0.0f) k.a[t] = lane_sel<K>(kCapA[K][t], k.a[t]);
+            if (kCapB[K][t] != 0.0f) k.b[t] = lane_sel<K>(kCapB[K][t], k.b[t]);
+        }
+    });
+    return k;
+}
+/* Lane c's capsule constants as one LDS row (ContactLdsT::capk): the select chains above stay
+ * inside the substep loop when the substep evaluates them (113 v_cndmask per substep), so the
+ * arm kernels evaluate them once per launch, park the row and read it back per substep with
+ * three ds_read_b128: (a, r) (b, flags | ns << 8 | (joint + 1) << 16) (tau_table, tau_plane,
+ * 4 * the row lane that holds the capsule's joint frame, 0). */
+struct CapRow {
+    CapEnds k;
+    CapLane cl;
+    float tt, tp;
+    int src4;
+};
+typedef float f4 __attribute__((ext_vector_type(4)));
+template <class LT>
+__device__ __forceinline__ void cap_row_fill(MRef m, LT& L, int c) {
+    static_assert(sizeof(L.capk) <= sizeof(L.capA) + sizeof(L.capB), "the rows fit where the end points were");
+    const int cc = c < PGX_NCAP ? c : 0;
+    const CapLane cl = cap_lane();
+    const CapEnds k = cap_ends_lane();
+    f4* row = reinterpret_cast<f4*>(L.capk[c]);
+    row[0] = (f4){k.a[0], k.a[1], k.a[2], cl.r};
+    row[1] = (f4){k.b[0], k.b[1], k.b[2], __int_as_float(cl.flags | (cl.ns << 8) | ((cl.j + 1) << 16))};
+    row[2] = (f4){cap_tau<TAU_TABLE>(m, cc), cap_tau<TAU_PLANE>(m, cc), __int_as_float((cl.j > 0 ? cl.j : 0) << 2), 0.0f};
+}
+template <class LT>
+__device__ __forceinline__ CapRow cap_row_load(LT& L, int c) {
+    /* (volatile: not promoted back into registers or re-derived in the loop; the LDS address
+     * space spelled out, or a volatile access stays a flat load at system scope) */
+    const auto* row = (const volatile __attribute__((address_space(3))) f4*)(L.capk[c]);
+    const f4 a = row[0], b = row[1], t = row[2];
+    const int fl = __float_as_int(b.w);
+    return CapRow{{{a.x, a.y, a.z}, {b.x, b.y, b.z}}, CapLane{a.w, fl & 255, (fl >> 8) & 255, (fl >> 16) - 1, 0},
+                  t.x, t.y, __float_as_int(t.z)};
+}
+/* Capsule c's world end points on lane c: the frame (R, o) of joint kCapJ[c] comes from the lane
+ * that holds it (lane j keeps joint j's in Rl / ol) by 12 ds_bpermute_b32, then
+ * A = o + R kCapA[c], B = o + R kCapB[c] once, in link_capsules' arithmetic.  Lanes 0 and
+ * >= PGX_NCAP get values nobody reads. */
+__device__ __forceinline__ void cap_ends_own(const M3& Rl, V3 ol, const CapRow& cr, V3& A, V3& B) {
+    static_assert(PGX_NCAP <= GW, "one capsule per lane of the row");
+    constexpr uint64_t ZA0 = zero_lanes(kCapA, 0, 0, 1), ZA1 = zero_lanes(kCapA, 1, 0, 1), ZA2 = zero_lanes(kCapA, 2, 0, 1);
+    static_assert(ZA0 == zero_lanes(kCapB, 0, 0, 1) && ZA1 == zero_lanes(kCapB, 1, 0, 1) && ZA2 == zero_lanes(kCapB, 2, 0, 1),
+                  "both ends of a capsule have the same zero components");
+    const int src = (int)((threadIdx.x & 63u & ~(unsigned)(GW - 1)) << 2) + cr.src4;
+    auto from = [&](float x) __attribute__((always_inline)) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, __builtin_bit_cast(int, x)));
+    };
+    M3 R;
+#pragma unroll
+    for (int t = 0; t < 9; t++) R.m[t] = from(Rl.m[t]);
+    const V3 o = v3(from(ol.x), from(ol.y), from(ol.z));
+    own_cols<ZA0, ZA1, ZA2>(R);
+    A = o + mull(R, cr.k.a);
+    B = o + mull(R, cr.k.b);
+}
+
 /* Robot capsule ends vs the table / plane in the wide layout (no object): lane c tests
- * capsule c's end spheres (the candidates of robot_contacts' table branch; at most 2 per
+ * capsule c's end spheres A, B (the candidates of robot_contacts' table branch; at most 2 per
  * pair); the row keeps the RB deepest by (depth, discovery order) like g1_insert -- ranked by
  * broadcast only when an env has more -- and every kept candidate goes straight to its id-ordered slot
  * (ids 2c + end grow with the lane), so sort_groups has nothing left to do. */
 template <class LT>
-__device__ __forceinline__ void robot_table_contacts_g(MRef m, const PgxDevEnv& e, LT& L, int es, int c) {
-    const int cc = c < PGX_NCAP ? c : 0;
-    const CapLane cl = cap_lane();
+__device__ __forceinline__ void robot_table_contacts_g(const PgxDevEnv& e, LT& L, int es, int c, V3 A, V3 B,
+                                                       const CapLane& cl, float tt, float tp) {
     const bool on = c < PGX_NCAP && (cl.flags & PGX_CAP_VS_TABLE);
-    const V3 A = lds3(L.capA[cc], es), B = lds3(L.capB[cc], es);
     const float r = cl.r;
     const bool two = cl.ns != 1;
-    /* each end against the box under it, within the pair's breaking threshold (cap_tau) */
-    const float tt = cap_tau<TAU_TABLE>(m, cc), tp = cap_tau<TAU_PLANE>(m, cc);
+    /* each end against the box under it, within the pair's breaking threshold (tt, tp: cap_tau) */
     const bool t0 = on_table(e, A.x, A.y), t1 = on_table(e, B.x, B.y);
     const float d0 = A.z - r - (t0 ? e.table_top : e.plane_z);
     const float d1 = B.z - r - (t1 ? e.table_top : e.plane_z);
@@ -1721,6 +1843,13 @@ __device__ __forceinline__ void robot_table_contacts_g(MRef m, const PgxDevEnv& 
         L.g1rb[sl][0][es] = 0.0f; L.g1rb[sl][1][es] = 0.0f; L.g1rb[sl][2][es] = 0.0f;
     }
     L.cnt[1][es] = __builtin_popcount(m0) + __builtin_popcount(m1);
+}
+/* (the end points from the LDS arrays link_capsules fills) */
+template <class LT>
+__device__ __forceinline__ void robot_table_contacts_g(MRef m, const PgxDevEnv& e, LT& L, int es, int c) {
+    const int cc = c < PGX_NCAP ? c : 0;
+    robot_table_contacts_g(e, L, es, c, lds3(L.capA[cc], es), lds3(L.capB[cc], es), cap_lane(), cap_tau<TAU_TABLE>(m, cc),
+                           cap_tau<TAU_PLANE>(m, cc));
 }
 
 /* Per-substep dynamics shared by both solver layouts: contact detection at the current
@@ -1937,11 +2066,14 @@ __device__ __forceinline__ void substep_dyn(MRef m, const PgxDevEnv& e, const fl
  * once instead of on all 16 lanes, and the results the redundant Cholesky needs (the
  * bias b, the lower triangle of M) are broadcast back.  Same equations as substep_dyn,
  * rearranged (below); only fp32 rounding differs. */
-struct LaneK {   /* link c's constants (lanes >= 7: zero) */
+struct LaneK {   /* link c's constants (lanes >= 7: zero; DAMP: lane 7 + b mass and com = kDmass[b], kDpos[b]) */
     float mass, com[3];
     float I[6], Iown[6];   /* inertia about the COM in the link frame (xx,yy,zz,xy,xz,yz); the
                               one its angular damping uses (link-7 group: the bodies' own) */
 };
+/* DAMP: link-7 damping body b's mass and position on the idle lane NJ + b, which forms its force
+ * (substep_dyn_g, OWN_DAMP); every use of mass and com as a link's is masked to lanes 0..6 */
+template <bool DAMP = false>
 __device__ __forceinline__ void lane_consts(LaneK& k) {
     k.mass = 0.0f;
 #pragma unroll
@@ -1961,6 +2093,16 @@ __device__ __forceinline__ void lane_consts(LaneK& k) {
             if (b != 0.0f) k.Iown[t] = lane_sel<j>(b, k.Iown[t]);
         }
     });
+    if constexpr (DAMP) {
+        static_assert(PGX_NDAMP <= GW - NJ, "one damping body per idle lane of the row");
+        sfor<0, PGX_NDAMP>([&](auto bc) __attribute__((always_inline)) {
+            constexpr int b = decltype(bc)::value;
+            k.mass = lane_sel<NJ + b>(kDmass[b], k.mass);
+#pragma unroll
+            for (int t = 0; t < 3; t++)
+                if (kDpos[b][t] != 0.0f) k.com[t] = lane_sel<NJ + b>(kDpos[b][t], k.com[t]);
+        });
+    }
 }
 /* inclusive prefix (suffix) sum over lanes 0..c (c..15) of each 16-lane row */
 __device__ __forceinline__ float row_pre(float x) {
@@ -2020,6 +2162,9 @@ template <int OBJ, int CONT, int AO = 0, int FULL = 0>
 __device__ __forceinline__ void substep_dyn_g(MRef m, const PgxDevEnv& e, const float* q, const float* qd,
                                               const ObjState& ob, ContactLdsGT<OBJ, FULL>* Lp, int es, Dyn& D, int c,
                                               const LaneK& K, bool check = false) {
+    /* lane owners: the arm kernels only.  The object and ReachAO kernels read other lanes' capsules
+     * from LDS and are register-tight (two waves per SIMD); they keep the redundant text */
+    constexpr bool OWN_CAPS = PGX_OWN_CAPS && CONT && !OBJ && !AO, OWN_DAMP = PGX_OWN_DAMP && !OBJ && !AO;
     M3 Rc;
     D.coll = false;
     if (OBJ) Rc = quat_mat(ob);
@@ -2076,7 +2221,7 @@ __device__ __forceinline__ void substep_dyn_g(MRef m, const PgxDevEnv& e, const 
             }
             z[j] = col(R, 2);
             o[j] = oj;
-            if constexpr (CONT) link_capsules(j, *Lp, es, R, oj);
+            if constexpr (CONT && !OWN_CAPS) link_capsules(j, *Lp, es, R, oj);
 #pragma unroll
             for (int t = 0; t < 9; t++) Rl.m[t] = lane_sel<j>(R.m[t], Rl.m[t]);
             ol = v3(lane_sel<j>(oj.x, ol.x), lane_sel<j>(oj.y, ol.y), lane_sel<j>(oj.z, ol.z));
@@ -2086,7 +2231,14 @@ __device__ __forceinline__ void substep_dyn_g(MRef m, const PgxDevEnv& e, const 
     }
     if (CONT) {
         if constexpr (!OBJ) {
-            robot_table_contacts_g(m, e, *Lp, es, c);
+            if constexpr (OWN_CAPS) {
+                const CapRow cr = cap_row_load(*Lp, c);
+                V3 A, B;
+                cap_ends_own(Rl, ol, cr, A, B);
+                robot_table_contacts_g(e, *Lp, es, c, A, B, cr.cl, cr.tt, cr.tp);
+            } else {
+                robot_table_contacts_g(m, e, *Lp, es, c);
+            }
             if constexpr (AO) {
                 /* obstacle contacts (ao_obstacle_candidates), lane-parallel: per obstacle, lane c
                  * measures capsule c's pair (the cull first, the exact query only where the pair
@@ -2308,13 +2460,44 @@ __device__ __forceinline__ void substep_dyn_g(MRef m, const PgxDevEnv& e, const 
         /* damping m v (k + k|v|): per link; the link-7 group per body (lane 6's values) */
         const V3 Fd = (K.mass * (m.lin_damp + m.lin_damp * norm(v))) * v;
         V3 Fg = v3(0, 0, 0), Tg = v3(0, 0, 0);
+        if constexpr (OWN_DAMP) {
+            /* body b on lane NJ + b (its position and mass: that lane's K.com, K.mass), from lane 6's
+             * frame and velocities (row_newbcast); lane 6 -- every lane -- then sums the four in
+             * the loop's order, from the same zero */
+            constexpr int S = NJ - 1;
+            /* a body on the link's z axis (x = y = 0): mulc's sum of its two dropped products is
+             * -0.0f, selected here instead of own_cols' -1 columns so that the broadcasts stay
+             * DPP operands of the products */
+            constexpr uint64_t Z0 = zero_lanes(kDpos, 0, NJ), Z1 = zero_lanes(kDpos, 1, NJ);
+            static_assert(Z0 == Z1 && zero_lanes(kDpos, 2, NJ) == 0, "a damping body is on the z axis or off both others");
+            float rbv[3];
 #pragma unroll
-        for (int b = 0; b < PGX_NDAMP; b++) {
-            const V3 rb = mulc(Rl, kDpos[b]);
-            const V3 vb = u + cross(w, rb);
-            const V3 fd = (kDmass[b] * (m.lin_damp + m.lin_damp * norm(vb))) * vb;
-            Fg = Fg + fd;
-            Tg = Tg + cross(ol + rb - cw, fd);
+            for (int r = 0; r < 3; r++) {
+                const float xy = pmul(bcast16<S>(Rl.m[3 * r]), K.com[0]) + pmul(bcast16<S>(Rl.m[3 * r + 1]), K.com[1]);
+                rbv[r] = (Z0 != 0 ? mask_sel<Z0>(-0.0f, xy) : xy) + pmul(bcast16<S>(Rl.m[3 * r + 2]), K.com[2]);
+            }
+            const V3 rb = v3(rbv[0], rbv[1], rbv[2]);
+            const V3 o6 = v3(bcast16<S>(ol.x), bcast16<S>(ol.y), bcast16<S>(ol.z));
+            const V3 c6 = v3(bcast16<S>(cw.x), bcast16<S>(cw.y), bcast16<S>(cw.z));
+            const V3 u6 = v3(bcast16<S>(u.x), bcast16<S>(u.y), bcast16<S>(u.z));
+            const V3 w6 = v3(bcast16<S>(w.x), bcast16<S>(w.y), bcast16<S>(w.z));
+            const V3 vb = u6 + cross(w6, rb);
+            const V3 fd = (K.mass * (m.lin_damp + m.lin_damp * norm(vb))) * vb;
+            const V3 td = cross(o6 + rb - c6, fd);
+            sfor<0, PGX_NDAMP>([&](auto bc) __attribute__((always_inline)) {
+                constexpr int b = NJ + decltype(bc)::value;
+                Fg = Fg + v3(bcast16<b>(fd.x), bcast16<b>(fd.y), bcast16<b>(fd.z));
+                Tg = Tg + v3(bcast16<b>(td.x), bcast16<b>(td.y), bcast16<b>(td.z));
+            });
+        } else {
+#pragma unroll
+            for (int b = 0; b < PGX_NDAMP; b++) {
+                const V3 rb = mulc(Rl, kDpos[b]);
+                const V3 vb = u + cross(w, rb);
+                const V3 fd = (kDmass[b] * (m.lin_damp + m.lin_damp * norm(vb))) * vb;
+                Fg = Fg + fd;
+                Tg = Tg + cross(ol + rb - cw, fd);
+            }
         }
         F = F + v3(lane_sel<NJ - 1>(Fg.x, Fd.x), lane_sel<NJ - 1>(Fg.y, Fd.y), lane_sel<NJ - 1>(Fg.z, Fd.z));
         T = T + v3(lane_sel<NJ - 1>(Tg.x, 0.0f), lane_sel<NJ - 1>(Tg.y, 0.0f), lane_sel<NJ - 1>(Tg.z, 0.0f));
@@ -5021,7 +5204,8 @@ __device__ __forceinline__ void step_body(const PgxDevModel* __restrict__ mdev, 
     }
     PGX_PROF_MARK(0);
     LaneK lk;
-    if constexpr (WIDE) lane_consts(lk);
+    if constexpr (WIDE) lane_consts<PGX_OWN_DAMP && !OBJ && !AO>(lk);
+    if constexpr (WIDE && CONT && !OBJ && !AO && PGX_OWN_CAPS) cap_row_fill(*fresh(mp), *L, c);
     const int n_substeps = e.n_substeps;
     bool collided = false;
     /* the pose the last substep starts from: getLinkState's cached pose (defined before the loop:

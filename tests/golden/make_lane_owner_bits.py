@@ -1,0 +1,154 @@
+"""Record the arm step kernels' raw output bits for tests/test_gpu_lane_owner_bits.py.
+
+lane_owner_bits.npz was made by this script on an MI355X with the libraries built from commit
+5c1a84c ("HER ring: collect transitions on the device, inside the step graph"), the parent of the
+change that gave each capsule's end points and each link-7 damping body a lane of its own in the
+wide layout's substep (substep_dyn_g).  That change has no switch inside one library, so the
+parent's bits are kept here: the claim is that every product, every contraction and every
+accumulation order stayed what link_capsules and the PGX_NDAMP loop computed on all 16 lanes.
+
+    python tests/golden/make_lane_owner_bits.py [OUT.npz]   (on the GPU box; PGX_LIB picks the library)
+
+Four cases, each 64 envs (one wave is 4 envs), 16 lanes per env, launch order = env order:
+
+    reach_random    PandaReach-v3, seeded random actions, 60 steps
+    joints_random   PandaReachJoints-v3, seeded random actions, 60 steps
+    joints_table    PandaReachJoints-v3 through the runtime-model library at the stock motor forces,
+                    the folding drive (fold() below): links other than the hand's tip come down on
+                    the table, 49 steps
+    joints_limp     PandaReachJoints-v3 through the runtime-model library with joint_forces x 0.05
+                    from limp_arm.start_state (seed 1), zero action, 30 steps: the arm collapses,
+                    and damping and bias are not hidden by the motors
+
+After the steps of RECORD[case] the bits of the observation, q, qd and of the robot slots' cached
+feature ids (2 * capsule + end; -1 = empty) as uint32, and per case the set of feature ids seen in
+the cache after any step ("<case>/features").  main() refuses to write a file whose feature sets
+do not cover an end sphere of every hand capsule (9-13) and of two arm-link capsules (1-8).
+"""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+for p in (ROOT, os.path.dirname(HERE)):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+N_ENVS, SEED = 64, 11
+CASES = ("reach_random", "joints_random", "joints_table", "joints_limp")
+ENV_OF = {"reach_random": "PandaReach-v3", "joints_random": "PandaReachJoints-v3",
+          "joints_table": "PandaReachJoints-v3", "joints_limp": "PandaReachJoints-v3"}
+RECORD = {"reach_random": (20, 40, 60), "joints_random": (20, 40, 60), "joints_table": (15, 30, 40, 49),
+          "joints_limp": (10, 20, 30)}
+NAMES = ("obs", "q", "qd", "ids")
+HAND_CAPS, ARM_CAPS = (9, 10, 11, 12, 13), (1, 2, 3, 4, 5, 6, 7, 8)
+GOLDEN = os.path.join(HERE, "lane_owner_bits.npz")
+
+
+def key(case, step, name):
+    return f"{case}/{step}/{name}"
+
+
+def fold(v, t):
+    """The folding drive, the same action at every step: the shoulder (dof 1) towards the table at
+    full rate, the elbow (dof 3) held in even envs and opening in odd ones, the wrist (dof 5)
+    either way by env quarter, the other joints a fixed random rate per env -- so that across the
+    64 envs different links arrive first.  Chosen on the fp64 oracle (signs of dofs 3 and 5 swept
+    until capsules on joints 5 and 6 pressed beside the last one); the recorded device run's cache
+    holds both end spheres of capsules 7, 8, 12 and 13, and joints_limp adds capsules 6 and 9-11."""
+    import torch
+
+    return torch.as_tensor(fold_actions(v.num_envs, v.action_dim), device="cuda:0")
+
+
+def fold_actions(n, ad):
+    a = np.random.default_rng(SEED).uniform(-1.0, 1.0, (n, ad)).astype(np.float32)
+    i = np.arange(n)
+    a[:, 1] = 1.0
+    a[:, 3] = np.where(i % 2 == 0, 0.0, 1.0)
+    a[:, 5] = np.where(i % 4 < 2, 1.0, -1.0)
+    return a
+
+
+def covered(features):
+    """(hand capsules, arm-link capsules) with an end sphere among the feature ids."""
+    caps = {int(f) // 2 for f in features}
+    return sorted(caps & set(HAND_CAPS)), sorted(caps & set(ARM_CAPS))
+
+
+def run(pg, case):
+    """{key: uint32 bits} of obs, q, qd and the robot slots' feature ids after each step of
+    RECORD[case], and the feature ids seen after any step."""
+    import torch
+
+    from panda_gym_amd import _native, abi
+
+    kw = {}
+    if case in ("joints_table", "joints_limp"):
+        rt = os.path.join(os.path.dirname(_native.LIB_PATH), "libpgx_rtmodel.so")
+        assert os.path.exists(rt), "libpgx_rtmodel.so is built by __graft_entry__.build()"
+        scale = 0.05 if case == "joints_limp" else 1.0
+        kw = {"lib_path": rt, "joint_forces": [f * scale for f in abi.JOINT_FORCES]}
+    old = os.environ.get("PGX_SORT_ENVS")
+    os.environ["PGX_SORT_ENVS"] = "0"   # read when the handle is created
+    try:
+        v = pg.PandaVecEnv(ENV_OF[case], num_envs=N_ENVS, device="cuda:0", seed=SEED, lanes_per_env=16, **kw)
+    finally:
+        if old is None:
+            del os.environ["PGX_SORT_ENVS"]
+        else:
+            os.environ["PGX_SORT_ENVS"] = old
+    v.reset_tensors(seed=SEED)
+    if case == "joints_limp":
+        import limp_arm as L
+
+        q, qd = L.start_state(v._cfg, N_ENVS, 1)
+        st = v.state()
+        qt = torch.as_tensor(q.T.copy(), dtype=torch.float32, device="cuda:0")
+        st["q"].copy_(qt)
+        st["qc"].copy_(qt)
+        st["qd"].copy_(torch.as_tensor(qd.T.copy(), dtype=torch.float32, device="cuda:0"))
+    budget = v.robot_contact_budget()
+    out, seen = {}, set()
+    for t in range(max(RECORD[case])):
+        if case == "joints_table":
+            a = fold(v, t)
+        elif case == "joints_limp":
+            a = torch.zeros((N_ENVS, v.action_dim), device="cuda:0")
+        else:
+            a = v.sample_actions(t).clone()
+        v.step_tensors(a)
+        st = v.state()
+        ids = st["contacts"][2 * abi.OBJECT_POINTS::2][:budget].contiguous().cpu().numpy()
+        seen |= {int(f) for f in np.unique(ids[ids >= 0])}
+        if t + 1 in RECORD[case]:
+            for name, x in (("obs", v.obs), ("q", st["q"]), ("qd", st["qd"])):
+                out[key(case, t + 1, name)] = x.contiguous().cpu().numpy().view(np.uint32).copy()
+            out[key(case, t + 1, "ids")] = ids.view(np.uint32).copy()
+    v.close()
+    out[f"{case}/features"] = np.array(sorted(seen), np.int32)
+    return out
+
+
+def main():
+    import panda_gym_amd as pg
+
+    pg.load_native()
+    out, feats = {}, set()
+    for case in CASES:
+        r = run(pg, case)
+        print(case, "features", r[f"{case}/features"].tolist())
+        feats |= set(r[f"{case}/features"].tolist())
+        out.update(r)
+    hand, arm = covered(feats)
+    print("hand capsules", hand, "arm-link capsules", arm)
+    assert hand == list(HAND_CAPS) and len(arm) >= 2, "the drive does not reach the coverage the test asserts"
+    path = sys.argv[1] if len(sys.argv) > 1 else GOLDEN
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes,", len(out), "arrays")
+
+
+if __name__ == "__main__":
+    main()
