@@ -3236,10 +3236,24 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
             gId[k] = L.g1id[k][es];
             gD[k] = L.g1d[k][es];
         };
+        /* (the previous substep may have held more than CGR_ALL robot points, and this substep's
+         * register point one of its slots CGR_ALL..RB_ALL-1 -- points of lower id gone: those slots
+         * are looked up where the wave has one in use, slots filling from 0; wave-uniform and rare,
+         * the same share of substeps as the extra rows) */
+        bool late_slots = false;
+        if constexpr (RB_ALL > CGR_ALL) late_slots = __any(L.cache[CACHE1 + 2 * CGR_ALL][es] >= 0.0f);
         /* a manifold point's warm start is its own applied impulse (btManifoldPoint::m_appliedImpulse
          * x the warm-starting factor), a fresh table point's its feature's cached one */
         auto warm_pt = [&](int w, float id) __attribute__((always_inline)) {
-            return (PERS && w >= 0) ? m.warmstart * L.mimp[w < 0 ? 0 : w][es] : warm_of(cid1, cim1, IC<CGR_ALL>{}, id);
+            if (PERS && w >= 0) return m.warmstart * L.mimp[w < 0 ? 0 : w][es];
+            float wm = warm_of(cid1, cim1, IC<CGR_ALL>{}, id);
+            if constexpr (RB_ALL > CGR_ALL) {
+                if (late_slots) {
+                    for (int s2 = CGR_ALL; s2 < RB_ALL; s2++)
+                        wm = L.cache[CACHE1 + 2 * s2][es] == id ? m.warmstart * L.cache[CACHE1 + 2 * s2 + 1][es] : wm;
+                }
+            }
+            return wm;
         };
         /* (ReachAO: points are rare and the o2 kernel's registers scarce: read per point) */
         if (!AO && __any(n1 > 0)) {

@@ -7,6 +7,13 @@ wide layout's substep (substep_dyn_g).  That change has no switch inside one lib
 parent's bits are kept here: the claim is that every product, every contraction and every
 accumulation order stayed what link_capsules and the PGX_NDAMP loop computed on all 16 lanes.
 
+Recorded again in round 12 from the same commit with one fix applied to its pgx_kernels.hip: a
+register point's warm start is looked up in every robot slot of the contact cache, not in the first
+four (substep_g's warm_pt; tests/test_gpu_whole_range.py found it).  The fix changes what the
+collapsing arm of joints_limp computes once a point moves up from slot 4..: against the first
+recording one env differs, 6 words of obs and q and 7 of qd at steps 20 and 30, and nothing else in
+the 56 arrays (profiles/r12/make_lane_owner_bits.log).
+
     python tests/golden/make_lane_owner_bits.py [OUT.npz]   (on the GPU box; PGX_LIB picks the library)
 
 Four cases, each 64 envs (one wave is 4 envs), 16 lanes per env, launch order = env order:

@@ -410,6 +410,69 @@ def test_ragged_batches_match_oracle(pg, oracle, env_id, n, lanes):
     venv.close()
 
 
+REGISTERED = [f"Panda{task}{control}{reward}-v3" for task in ("Reach", "Push", "PickAndPlace")
+              for control in ("", "Joints") for reward in ("", "Dense")] + ["PandaReachAO-v3"]
+
+
+@pytest.mark.parametrize("env_id", REGISTERED)
+def test_every_registered_id_matches_oracle(pg, oracle, env_id, lanes):
+    """Every registered env id (13), both layouts: 67 envs, reset_tensors(seed=17), three random steps,
+    the state copied to the oracle before each (as test_ragged_batches_match_oracle) -- observation
+    and achieved goal within OBS_TOL, desired goal and flags equal (ReachAO's collision flag with that
+    test's margin rule), the sparse reward equal off the 1e-5 threshold edge, the dense reward
+    within OBS_TOL; shapes against the spec's obs_dim / action_dim.  Measured, largest over ids,
+    layouts and steps (profiles/r12/pytest_gpu_registered_ids.log): observation 2.6e-5 (ReachAO;
+    the others 2.1e-5), achieved goal 3.3e-7, dense reward 1.0e-6; no env within 1e-5 of the
+    threshold, none ended."""
+    n = 67
+    spec = pg.spec(env_id)
+    assert sorted(REGISTERED) == pg.registered_ids()
+    venv = pg.PandaVecEnv(env_id, num_envs=n, device="cuda:0", seed=17, lanes_per_env=lanes)
+    venv.reset_tensors(seed=17)
+    assert (venv.obs_dim, venv.action_dim) == (spec.obs_dim, spec.action_dim)
+    ref = oracle.OracleVecEnv(venv._cfg, n)
+    assert (ref.od, ref.ad) == (spec.obs_dim, spec.action_dim)
+    ao, dense = env_id == "PandaReachAO-v3", "Dense" in env_id
+    for t in range(3):
+        _state_to_oracle(venv, ref)
+        goal = ref.goal.copy()
+        acts = venv.sample_actions(t).clone()
+        assert tuple(acts.shape) == (n, spec.action_dim)
+        venv.step_tensors(acts)
+        out = ref.step(acts.cpu().numpy(), margins=ao)
+        obs, ag, dg, rew, succ = _gpu_out(venv)
+        assert obs.shape == out["obs"].shape == (n, spec.obs_dim) and ag.shape == dg.shape == (n, 3)
+        assert rew.shape == succ.shape == (n,)
+        assert np.all(np.isfinite(obs)) and np.all(np.isfinite(rew))
+        tr, te = venv.truncated.cpu().numpy(), venv.terminated.cpu().numpy()
+        same = tr == out["truncated"]
+        if ao:   # test_gpu_reach_ao.py, FLIP_MARGIN
+            assert np.all(same | (out["margin_abs"] < 1e-6)), t
+        else:
+            assert np.all(same) and not tr.any(), t
+        # the threshold edge: the distance of the step's own achieved goal (an ended env is reset and
+        # reports the next episode's)
+        ended = (out["truncated"] | out["terminated"]) != 0
+        assert ao or not ended.any(), t
+        ag_t = np.where(ended[:, None], out["terminal_obs"][:, :3], out["ag"])   # (ReachAO: the EE position)
+        d = np.linalg.norm(ag_t.astype(np.float64) - goal, axis=-1)
+        safe = same & (np.abs(d - spec.distance_threshold) > EDGE)
+        assert np.array_equal(succ[safe], out["success"][safe]) and np.array_equal(te[safe], out["terminated"][safe]), t
+        keep = same & (tr == 0)
+        e_obs = np.abs(obs[keep] - out["obs"][keep]).max(initial=0.0)
+        e_ag = np.abs(ag[keep] - out["ag"][keep]).max(initial=0.0)
+        e_rew = np.abs(rew[keep & safe] - out["reward"][keep & safe]).max(initial=0.0)
+        print(f"\n{env_id} lanes {lanes} step {t}: obs {e_obs:.2e}, achieved goal {e_ag:.2e}, reward {e_rew:.2e}, "
+              f"off the edge {int(safe.sum())} of {n}, ended {int(tr.sum())} + {int(te.sum())}")
+        assert e_obs <= OBS_TOL and e_ag <= OBS_TOL, (t, e_obs, e_ag)
+        assert np.array_equal(dg[keep], out["dg"][keep]), t
+        if dense:
+            assert np.abs(rew[keep] - out["reward"][keep]).max(initial=0.0) <= OBS_TOL, t
+        else:
+            assert np.array_equal(rew[keep & safe], out["reward"][keep & safe]), t
+    venv.close()
+
+
 @pytest.mark.parametrize("env_id", ["PandaReach-v3", "PandaPickAndPlace-v3", "PandaReachAO-v3"])
 def test_single_env_robot_task_sim_views(pg, env_id):
     """`env.robot`, `env.task`, `env.sim` of the single-env wrapper (RobotTaskEnv's attributes,
