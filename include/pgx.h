@@ -952,6 +952,112 @@ int pgx_rollout_set_last(pgx_rollout_handle h, const float* obs, const float* ac
 int pgx_rollout_state(pgx_rollout_handle h, int32_t* pos, uint32_t* errors, int32_t clear, void* stream);
 int pgx_rollout_arrays(pgx_rollout_handle h, pgx_rollout_views* out);
 
+/* ----------------------------------------------------------------------
+ * Actor: stable-baselines3's off-policy actor forward on the device (pgx_actor.hip), one launch
+ * that reads the observation buffers of an env (or of a VecNormalize) and writes the action
+ * buffer the next pgx_step reads, so observe -> act -> step -> collect captures into one graph.
+ *
+ * Features (SB3 CombinedExtractor over the Dict space, sorted keys), in_dim = obs_dim + 6:
+ *   x = achieved_goal[3] | desired_goal[3] | observation[obs_dim]
+ * Trunk: n_layers x (Linear + ReLU), widths hidden[l] in 1..512; relu(v) = v > 0 ? v : +0.
+ * Heads: PGX_ACTOR_GAUSSIAN (SAC / TQC): mu and log_std, [action_dim] each;
+ *        PGX_ACTOR_DETERMINISTIC (TD3 / DDPG): mu.
+ *
+ * Arithmetic contract (f32; what pgx_actor_forward_host restates and the kernel's f32-input MFMA
+ * gives bit for bit).  Every Linear output o over inputs x[0..K):
+ *   acc = bias[o];  for k = 0, 1, ..., K16 - 1 in ascending order:  acc = fmaf(x[k], W[o][k], acc)
+ * THE ACCUMULATOR STARTS AT THE BIAS; nothing is added afterwards.  K16 = K rounded up to a
+ * multiple of 16: the terms k >= K are fmaf(+0, +0, acc), which leave every accumulator but -0 as
+ * it is (a -0 accumulator needs a -0 bias and only -0 products, and becomes +0).  One accumulator
+ * per output, no split of the k range, no reassociation.
+ *   mean    = mu's output; with clip_mean > 0: mean < -clip_mean ? -clip_mean : mean > clip_mean ?
+ *             clip_mean : mean   (SB3's gSDE actor, Hardtanh); the `mean` debug plane holds this
+ *   log_std = log_std's output v: v < -20 ? -20 : v > 2 ? 2 : v   (SB3 LOG_STD_MIN / LOG_STD_MAX)
+ * Epilogue (f32, device tanhf / expf):
+ *   GAUSSIAN:       action = tanhf(deterministic ? mean : fmaf(expf(log_std), eps, mean))
+ *   DETERMINISTIC:  a = tanhf(mean); with noise (deterministic == 0): a = a + fmaf(noise_sigma, eps,
+ *                   noise_mu) (SB3 _sample_action with NormalActionNoise); action = clip(a, -1, 1)
+ *
+ * Noise eps [N, action_dim]: the caller's buffer (io.eps), or, with io.eps NULL and deterministic
+ * == 0, the device Philox4x32-10 stream: for env e and dimension pair p = d / 2
+ *   r = philox(counter = (step lo, step hi, e, 0x41435430 ^ p), key = (seed lo, seed hi))
+ *   u1 = ((r[0] >> 8) + 1) * 2^-24 in (0, 1],  u2 = (r[1] >> 8) * 2^-24 in [0, 1)
+ *   rad = sqrtf(-2 logf(u1)), ang = 6.2831855f * u2
+ *   eps[e][2 p] = rad * cosf(ang),  eps[e][2 p + 1] = rad * sinf(ang)        (r[2], r[3] unused)
+ * `step` is a 64-bit device word (pgx_actor_state): a forward that draws from the stream adds one
+ * to it behind its last read, inside the same launch, so every replay of a captured graph draws
+ * new noise.  A forward with io.eps or with deterministic != 0 leaves the word alone.
+ *
+ * Weights are packed at pgx_actor_set_weights into the handle's buffers, per Linear as
+ *   P[kb][tile][lane][i] = W[16 tile + (lane & 15)][16 kb + 4 i + (lane >> 4)], zero where W ends
+ * (one 16-byte load per lane feeds four 16x16x4 MFMA steps); both heads share one tile, mu in
+ * rows 0..6 and log_std in rows 8..14.
+ * ---------------------------------------------------------------------- */
+typedef struct pgx_actor* pgx_actor_handle;
+
+#define PGX_ACTOR_GAUSSIAN 0
+#define PGX_ACTOR_DETERMINISTIC 1
+#define PGX_ACTOR_MAX_LAYERS 3
+#define PGX_ACTOR_MAX_WIDTH 512
+#define PGX_ACTOR_MAX_ACTION 7
+#define PGX_ACTOR_LOG_STD_MIN -20.0f
+#define PGX_ACTOR_LOG_STD_MAX 2.0f
+
+typedef struct pgx_actor_config {
+    int32_t n_envs;
+    int32_t obs_dim;
+    int32_t action_dim;           /* 1..7 */
+    int32_t n_layers;             /* 1..3 hidden layers */
+    int32_t hidden[3];            /* widths of the first n_layers, 1..512 each */
+    int32_t kind;                 /* PGX_ACTOR_GAUSSIAN / PGX_ACTOR_DETERMINISTIC */
+    double clip_mean;             /* >= 0; 0: off */
+    double noise_mu;              /* DETERMINISTIC: NormalActionNoise mean */
+    double noise_sigma;           /* >= 0 */
+    uint64_t seed;                /* Philox key of the noise stream */
+} pgx_actor_config;
+
+/* torch-layout f32 parameters, device or host pointers: weight[l] [out, in] row-major and bias[l]
+ * [out] for the hidden layers l < n_layers, then mu at index n_layers and, GAUSSIAN only, log_std
+ * at index n_layers + 1. */
+typedef struct pgx_actor_weights {
+    const float* weight[5];
+    const float* bias[5];
+} pgx_actor_weights;
+
+/* Device pointers of one forward.  Only `action` and the non-NULL debug planes are written. */
+typedef struct pgx_actor_io {
+    const float* obs;             /* [N,obs_dim] */
+    const float* achieved_goal;   /* [N,3] */
+    const float* desired_goal;    /* [N,3] */
+    float* action;                /* [N,action_dim] */
+    const float* eps;             /* [N,action_dim] or NULL: the device stream */
+    float* mean_out;              /* debug [N,action_dim] or NULL: mean (after clip_mean) */
+    float* log_std_out;           /* debug [N,action_dim] or NULL: log_std after the clamp (GAUSSIAN) */
+    float* eps_out;               /* debug [N,action_dim] or NULL: the noise used (0 when deterministic) */
+    uint32_t* philox_out;         /* debug [N,4,4] or NULL: r[0..3] of every pair p < (action_dim + 1) / 2,
+                                     written when the device stream is drawn from */
+} pgx_actor_io;
+
+/* PGX_E_INVALID, before any device call and naming the field, for n_envs <= 0, obs_dim <= 0 (or
+ * above 4096), action_dim outside 1..7, n_layers outside 1..3, a hidden width outside 1..512, an
+ * unknown kind, a negative or NaN clip_mean / noise_sigma, a non-finite noise_mu, NULL cfg / out. */
+int pgx_actor_create(const pgx_actor_config* cfg, int device, pgx_actor_handle* out);
+void pgx_actor_destroy(pgx_actor_handle h);
+/* Copies the parameters into the handle and packs them there, on `stream`: a captured graph sees
+ * them at its next replay.  The sources must stay valid until the stream has run the copies. */
+int pgx_actor_set_weights(pgx_actor_handle h, const pgx_actor_weights* w, void* stream);
+/* One launch (see above). */
+int pgx_actor_forward(pgx_actor_handle h, const pgx_actor_io* io, int32_t deterministic, void* stream);
+/* The noise step word after synchronising `stream`; set: synchronises, then writes it. */
+int pgx_actor_state(pgx_actor_handle h, uint64_t* step, void* stream);
+int pgx_actor_set_state(pgx_actor_handle h, uint64_t step, void* stream);
+/* The arithmetic contract above in plain C++ on host arrays (std::fmaf), for n rows: mean [n,
+ * action_dim] and, GAUSSIAN with log_std_out != NULL, log_std.  cfg->n_envs is not read.  Never
+ * touches a device; not a stepping path. */
+int pgx_actor_forward_host(const pgx_actor_config* cfg, const pgx_actor_weights* w, const float* obs,
+                           const float* achieved_goal, const float* desired_goal, int32_t n, float* mean_out,
+                           float* log_std_out);
+
 #ifdef __cplusplus
 }
 #endif

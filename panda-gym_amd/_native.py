@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 from .abi import PGX_E_INVALID  # noqa: F401 (re-exported for the C-ABI tests)
-from .abi import (PgxConfig, PgxMonitorConfig, PgxMonitorIo, PgxMonitorTotals, PgxNormConfig, PgxNormIo, PgxReplayBatch,
+from .abi import (PgxActorConfig, PgxActorIo, PgxActorWeights, PgxConfig, PgxMonitorConfig, PgxMonitorIo, PgxMonitorTotals, PgxNormConfig, PgxNormIo, PgxReplayBatch,
                   PgxReplayConfig, PgxReplayStep, PgxReplayViews, PgxRolloutBatch, PgxRolloutConfig, PgxRolloutIo,
                   PgxRolloutViews, PgxStateView, PgxStepOut, PgxTransition)
 
@@ -31,6 +31,8 @@ EXPORTS = [
     "pgx_rollout_row_dim", "pgx_rollout_row_stride", "pgx_rollout_create", "pgx_rollout_destroy", "pgx_rollout_add",
     "pgx_rollout_compute_returns_and_advantage", "pgx_rollout_permutation", "pgx_rollout_gather", "pgx_rollout_reset",
     "pgx_rollout_set_last", "pgx_rollout_state", "pgx_rollout_arrays",
+    "pgx_actor_create", "pgx_actor_destroy", "pgx_actor_set_weights", "pgx_actor_forward", "pgx_actor_state",
+    "pgx_actor_set_state", "pgx_actor_forward_host",
 ]
 
 
@@ -129,6 +131,15 @@ def load(path: str = None):
     lib.pgx_rollout_set_last.argtypes = [C.c_void_p] * 6
     lib.pgx_rollout_state.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int32, C.c_void_p]
     lib.pgx_rollout_arrays.argtypes = [C.c_void_p, C.POINTER(PgxRolloutViews)]
+    lib.pgx_actor_create.argtypes = [C.POINTER(PgxActorConfig), C.c_int, C.POINTER(C.c_void_p)]
+    lib.pgx_actor_destroy.argtypes = [C.c_void_p]
+    lib.pgx_actor_destroy.restype = None
+    lib.pgx_actor_set_weights.argtypes = [C.c_void_p, C.POINTER(PgxActorWeights), C.c_void_p]
+    lib.pgx_actor_forward.argtypes = [C.c_void_p, C.POINTER(PgxActorIo), C.c_int32, C.c_void_p]
+    lib.pgx_actor_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
+    lib.pgx_actor_set_state.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.pgx_actor_forward_host.argtypes = [C.POINTER(PgxActorConfig), C.POINTER(PgxActorWeights), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     _libs[path] = lib
     return lib
 

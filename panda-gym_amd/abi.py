@@ -255,6 +255,34 @@ class PgxRolloutViews(C.Structure):
     ]
 
 
+# Actor (include/pgx.h, pgx_actor_*)
+ACTOR_GAUSSIAN, ACTOR_DETERMINISTIC = 0, 1
+ACTOR_KINDS = {"gaussian": ACTOR_GAUSSIAN, "deterministic": ACTOR_DETERMINISTIC}
+ACTOR_MAX_LAYERS, ACTOR_MAX_WIDTH, ACTOR_MAX_ACTION = 3, 512, 7
+ACTOR_LOG_STD_MIN, ACTOR_LOG_STD_MAX = -20.0, 2.0
+ACTOR_PHILOX_TAG = 0x41435430   # counter word 3 of the noise stream, xor the dimension pair
+
+
+class PgxActorConfig(C.Structure):
+    _fields_ = [
+        ("n_envs", C.c_int32), ("obs_dim", C.c_int32), ("action_dim", C.c_int32), ("n_layers", C.c_int32),
+        ("hidden", C.c_int32 * 3), ("kind", C.c_int32), ("clip_mean", C.c_double), ("noise_mu", C.c_double),
+        ("noise_sigma", C.c_double), ("seed", C.c_uint64),
+    ]
+
+
+class PgxActorWeights(C.Structure):
+    _fields_ = [("weight", C.c_void_p * 5), ("bias", C.c_void_p * 5)]
+
+
+class PgxActorIo(C.Structure):
+    _fields_ = [
+        ("obs", C.c_void_p), ("achieved_goal", C.c_void_p), ("desired_goal", C.c_void_p), ("action", C.c_void_p),
+        ("eps", C.c_void_p), ("mean_out", C.c_void_p), ("log_std_out", C.c_void_p), ("eps_out", C.c_void_p),
+        ("philox_out", C.c_void_p),
+    ]
+
+
 def rollout_row_fields(obs_dim: int, action_dim: int):
     """(name, offset, width) of the RolloutBuffer batch row layout of include/pgx.h, plus row_dim."""
     f, o = [], 0

@@ -1,0 +1,266 @@
+"""Device-resident actor: stable-baselines3's off-policy actor forward as one HIP launch.
+
+The reference trains SB3 off-policy algorithms with ``MultiInputPolicy`` and ``net_arch`` [256, 256] or
+[400, 300] (setup_training.py, hyperparameters.py): TQC / SAC act through a squashed Gaussian, TD3 /
+DDPG through a deterministic actor with ``NormalActionNoise``, every evaluation with
+``deterministic=True``.  ``Actor`` is that forward pass -- CombinedExtractor's concatenation, the
+Linear + ReLU trunk, the heads, the squash and the noise -- in libpgx.so (pgx_actor.hip; C-ABI and the
+arithmetic contract in include/pgx.h, section "Actor").  It reads the persistent observation buffers
+of an env or a wrapper and writes the action buffer the next step reads, so ``capture_rollout`` puts
+``k`` closed-loop steps of observe, act, step, collect into one graph.  No CPU fallback: with
+``device="cpu"`` an ``Actor`` only holds and maps parameters (``load_state_dict`` / ``state_dict`` /
+``forward_host``, the host model of the kernel's arithmetic, which is a test oracle and not a way to step).
+
+Training -- critics, optimiser, gSDE exploration, PPO's actor-critic -- is not here.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import abi
+from ._native import PgxError, check, load
+
+try:
+    import torch
+except ImportError:  # pragma: no cover
+    torch = None
+
+OBS_KEYS = ("observation", "achieved_goal", "desired_goal")
+
+
+class Actor:
+    """SB3's SAC / TQC (``kind="gaussian"``) or TD3 / DDPG (``kind="deterministic"``) actor on the device.
+
+    ``env``: a ``PandaVecEnv`` or a wrapper of one (``n_envs``, the dims and the device are read from
+    it), or pass ``obs_dim``, ``action_dim`` and ``n_envs``.  ``net_arch``: 1 to 3 hidden widths of 1
+    to 512.  ``clip_mean`` > 0: SB3's gSDE actor ``Hardtanh`` on the mean (what a ``use_sde=True``
+    model needs for deterministic evaluation).  ``action_noise``: ``(mu, sigma)`` of SB3's
+    ``NormalActionNoise`` for the deterministic kind (None: no noise, every call is deterministic).
+    Parameters are zero until ``load_state_dict``."""
+
+    def __init__(self, env: Any = None, obs_dim: Optional[int] = None, action_dim: Optional[int] = None,
+                 net_arch: Sequence[int] = (256, 256), kind: str = "gaussian", clip_mean: float = 0.0,
+                 action_noise: Optional[Tuple[float, float]] = None, seed: int = 0, device: Any = None,
+                 n_envs: Optional[int] = None):
+        if torch is None:
+            raise PgxError("Actor needs torch for its buffers")
+        if kind not in abi.ACTOR_KINDS:
+            raise ValueError(f"kind must be one of {list(abi.ACTOR_KINDS)}, got {kind!r}")
+        if env is not None:
+            n_envs = env.num_envs
+            obs_dim = env.obs_dim if obs_dim is None else obs_dim
+            action_dim = env.action_dim if action_dim is None else action_dim
+            device = env.device if device is None else device
+        if obs_dim is None or action_dim is None or n_envs is None:
+            raise ValueError("pass env, or obs_dim, action_dim and n_envs")
+        if int(n_envs) <= 0:
+            raise ValueError("n_envs must be > 0")
+        self.lib = load()
+        self.device = torch.device("cuda:0" if device is None else device)
+        self.n_envs, self.obs_dim, self.action_dim = int(n_envs), int(obs_dim), int(action_dim)
+        self.net_arch = tuple(int(w) for w in net_arch)
+        self.kind, self.clip_mean, self.seed = kind, float(clip_mean), int(seed)
+        self.action_noise = None if action_noise is None else (float(action_noise[0]), float(action_noise[1]))
+        if kind == "gaussian" and action_noise is not None:
+            raise ValueError("action_noise belongs to the deterministic kind (SB3 NormalActionNoise)")
+        cfg = abi.PgxActorConfig()
+        cfg.n_envs, cfg.obs_dim, cfg.action_dim = self.n_envs, self.obs_dim, self.action_dim
+        cfg.n_layers = len(self.net_arch)
+        for i, w in enumerate(self.net_arch[:abi.ACTOR_MAX_LAYERS]):
+            cfg.hidden[i] = w
+        cfg.kind, cfg.clip_mean = abi.ACTOR_KINDS[kind], self.clip_mean
+        cfg.noise_mu, cfg.noise_sigma = self.action_noise or (0.0, 0.0)
+        cfg.seed = self.seed & 0xFFFFFFFFFFFFFFFF
+        self._cfg = cfg
+        self._h = None
+        # the parameters as given (torch layout), on the actor's device: what set_weights reads
+        dims = [self.obs_dim + 6] + list(self.net_arch)
+        shapes = [(dims[i + 1], dims[i]) for i in range(len(self.net_arch))]
+        shapes += [(self.action_dim, dims[-1])] * (2 if kind == "gaussian" else 1)
+        self._names = self._key_names(kind, len(self.net_arch))
+        self._w = [torch.zeros(s, dtype=torch.float32, device=self.device) for s in shapes]
+        self._b = [torch.zeros(s[0], dtype=torch.float32, device=self.device) for s in shapes]
+        self.actions = torch.zeros((self.n_envs, self.action_dim), dtype=torch.float32, device=self.device)
+        self._debug: Optional[Dict[str, "torch.Tensor"]] = None
+        self._keep: List[Any] = []
+        if self.device.type == "cuda":
+            h = C.c_void_p()
+            torch.cuda.set_device(self.device)
+            check(self.lib.pgx_actor_create(C.byref(cfg), self.device.index or 0, C.byref(h)), "pgx_actor_create",
+                  self.lib)
+            self._h = h
+            self._push()
+        else:   # the library's argument checks either way: the host model on no rows
+            self.forward_host({"observation": np.zeros((0, self.obs_dim), np.float32),
+                               "achieved_goal": np.zeros((0, 3), np.float32), "desired_goal": np.zeros((0, 3), np.float32)})
+
+    # ------------------------------------------------------------ plumbing
+    @staticmethod
+    def _key_names(kind: str, n_layers: int) -> List[str]:
+        """SB3's module names per parameter slot: the hidden layers, mu, log_std."""
+        if kind == "gaussian":   # sac/policies.py Actor: latent_pi = Sequential(Linear, ReLU, ...), mu, log_std
+            return [f"latent_pi.{2 * i}" for i in range(n_layers)] + ["mu", "log_std"]
+        # td3/policies.py Actor: mu = Sequential(Linear, ReLU, ..., Linear, Tanh)
+        return [f"mu.{2 * i}" for i in range(n_layers + 1)]
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _need_device(self):
+        if self._h is None:
+            raise PgxError("this Actor has no device handle (device='cpu' or closed): no CPU fallback")
+
+    def _weights_struct(self, ws, bs) -> abi.PgxActorWeights:
+        w = abi.PgxActorWeights()
+        for i, (x, y) in enumerate(zip(ws[:5], bs[:5])):   # (more: the library rejects n_layers)
+            w.weight[i], w.bias[i] = x, y
+        return w
+
+    def _push(self) -> None:
+        w = self._weights_struct([t.data_ptr() for t in self._w], [t.data_ptr() for t in self._b])
+        check(self.lib.pgx_actor_set_weights(self._h, C.byref(w), self._stream()), "pgx_actor_set_weights", self.lib)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            torch.cuda.synchronize(self.device)
+            self.lib.pgx_actor_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ----------------------------------------------------------- parameters
+    def state_dict(self) -> Dict[str, "torch.Tensor"]:
+        """The parameters under SB3's actor key names (copies, on the actor's device)."""
+        out = {}
+        for name, w, b in zip(self._names, self._w, self._b):
+            out[f"{name}.weight"], out[f"{name}.bias"] = w.clone(), b.clone()
+        return out
+
+    def load_state_dict(self, sd: Dict[str, Any]) -> None:
+        """Load SB3 actor parameters: ``latent_pi.{0,2,4}`` / ``mu`` / ``log_std`` (SAC, TQC) or
+        ``mu.{0,2,4,...}`` (TD3, DDPG), ``.weight`` [out, in] and ``.bias`` [out]; a policy's state
+        dict works too (its ``actor.`` keys are read, the rest ignored).  The packed weights in the
+        handle are replaced on the current stream: a captured graph uses them at its next replay."""
+        if any(k.startswith("actor.") for k in sd):
+            sd = {k[len("actor."):]: v for k, v in sd.items() if k.startswith("actor.")}
+        new_w, new_b = [], []
+        for name, w, b in zip(self._names, self._w, self._b):
+            for key, cur, dst in ((f"{name}.weight", w, new_w), (f"{name}.bias", b, new_b)):
+                if key not in sd:
+                    raise KeyError(f"load_state_dict: missing key {key!r}")
+                v = sd[key]
+                t = v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
+                if tuple(t.shape) != tuple(cur.shape):
+                    raise ValueError(f"load_state_dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(cur.shape)}")
+                dst.append(t.to(device=self.device, dtype=torch.float32).contiguous())
+        for cur, new in zip(self._w + self._b, new_w + new_b):
+            cur.copy_(new)   # in place: the handle's copies read these same buffers
+        if self._h is not None:
+            self._push()
+
+    # --------------------------------------------------------------- forward
+    def enable_debug(self) -> Dict[str, "torch.Tensor"]:
+        """Allocate the debug planes every later forward fills: ``mean`` (after ``clip_mean``),
+        ``log_std`` (after the clamp), ``eps`` [N, A] f32 and ``philox`` [N, 4, 4] int32 (the words of
+        the device noise stream).  Tests and tools only."""
+        if self._debug is None:
+            z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=self.device)  # noqa: E731
+            N, A = self.n_envs, self.action_dim
+            self._debug = {"mean": z(N, A), "log_std": z(N, A), "eps": z(N, A), "philox": z(N, 4, 4, dt=torch.int32)}
+        return self._debug
+
+    def _launch(self, obs: Dict[str, "torch.Tensor"], deterministic: bool, eps: Optional["torch.Tensor"]) -> None:
+        d = self._debug
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        io = abi.PgxActorIo(p(obs["observation"]), p(obs["achieved_goal"]), p(obs["desired_goal"]), p(self.actions),
+                            p(eps), *([None] * 4 if d is None else [p(d[k]) for k in ("mean", "log_std", "eps", "philox")]))
+        det = 1 if (deterministic or (self.kind == "deterministic" and self.action_noise is None)) else 0
+        check(self.lib.pgx_actor_forward(self._h, C.byref(io), det, self._stream()), "pgx_actor_forward", self.lib)
+
+    def _dev(self, x, shape) -> "torch.Tensor":
+        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+        if tuple(t.shape) != shape:
+            raise ValueError(f"expected shape {list(shape)}, got {list(t.shape)}")
+        return t.to(device=self.device, dtype=torch.float32).contiguous()   # a no-op for the env's own buffers
+
+    def __call__(self, obs: Dict[str, Any], deterministic: bool = False, eps: Any = None) -> "torch.Tensor":
+        """Actions [N, A] for the observation dict ``obs`` (what ``step_tensors`` / ``reset_tensors`` of
+        an env, a ``VecNormalize`` or a ``VecMonitor`` return; read in place): one launch.  ``eps``
+        [N, A]: the Gaussian noise to use instead of the device stream.  Returns the actor's
+        persistent action tensor (overwritten by the next call)."""
+        self._need_device()
+        N = self.n_envs
+        o = {k: self._dev(obs[k], (N, self.obs_dim if k == "observation" else 3)) for k in OBS_KEYS}
+        e = None if eps is None else self._dev(eps, (N, self.action_dim))
+        self._launch(o, deterministic, e)
+        self._keep = [o, e]   # alive until the stream has consumed them
+        return self.actions
+
+    forward = __call__
+
+    def forward_host(self, obs: Dict[str, Any]):
+        """``(mean, log_std)`` [n, A] numpy f32 from the library's host model of the kernel's arithmetic
+        (``log_std`` None for the deterministic kind), for any number of rows.  A test oracle."""
+        o = {k: np.ascontiguousarray(obs[k].cpu().numpy() if torch.is_tensor(obs[k]) else obs[k], dtype=np.float32)
+             for k in OBS_KEYS}
+        n = o["observation"].shape[0]
+        ws = [np.ascontiguousarray(t.cpu().numpy()) for t in self._w]
+        bs = [np.ascontiguousarray(t.cpu().numpy()) for t in self._b]
+        w = self._weights_struct([x.ctypes.data for x in ws], [x.ctypes.data for x in bs])
+        mean = np.zeros((n, self.action_dim), np.float32)
+        log_std = np.zeros((n, self.action_dim), np.float32) if self.kind == "gaussian" else None
+        check(self.lib.pgx_actor_forward_host(C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
+                                              abi.ptr(o["achieved_goal"]), abi.ptr(o["desired_goal"]), n, abi.ptr(mean),
+                                              abi.ptr(log_std)), "pgx_actor_forward_host", self.lib)
+        return mean, log_std
+
+    @property
+    def noise_step(self) -> int:
+        """The device word that counts the forwards that drew noise from the Philox stream (this
+        synchronises).  Setting it back reproduces the draws."""
+        self._need_device()
+        v = C.c_uint64(0)
+        check(self.lib.pgx_actor_state(self._h, C.byref(v), self._stream()), "pgx_actor_state", self.lib)
+        return int(v.value)
+
+    @noise_step.setter
+    def noise_step(self, value: int) -> None:
+        self._need_device()
+        check(self.lib.pgx_actor_set_state(self._h, C.c_uint64(int(value) & 0xFFFFFFFFFFFFFFFF), self._stream()),
+              "pgx_actor_set_state", self.lib)
+
+    # --------------------------------------------------------------- capture
+    def capture_rollout(self, venv, k: int, deterministic: bool = False, after_step: Optional[Callable[[], None]] = None):
+        """Capture ``k`` closed-loop steps into one HIP graph (``torch.cuda.CUDAGraph``): the forward
+        on ``venv``'s persistent observation buffers (through a ``VecNormalize`` the normalised ones),
+        ``venv._enqueue_step(self.actions)``, ``after_step()`` -- the loop of ``capture_steps`` with the
+        policy inside.  ``venv``: the env, a ``VecNormalize`` or a ``VecMonitor``.  ``after_step``: e.g.
+        ``buf.after_step(venv, actor.actions)`` of the HER ring.  Capture runs nothing; every replay
+        draws new noise (the step word is on the device) and uses the weights loaded last."""
+        from .rollout import step_buffers
+
+        self._need_device()
+        obs = step_buffers(venv)[0]
+        N = self.n_envs
+        for key in OBS_KEYS:
+            t = obs[key]
+            if tuple(t.shape) != (N, self.obs_dim if key == "observation" else 3) or t.dtype != torch.float32 \
+                    or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"venv's {key} buffer does not fit this actor")
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(int(k)):
+                self._launch(obs, deterministic, None)
+                venv._enqueue_step(self.actions, "pgx_step (capture)")
+                if after_step is not None:
+                    after_step()
+        g._pgx_keep = (self, obs)   # the graph reads these buffers at replay
+        return g

@@ -321,9 +321,22 @@ class HerReplayBuffer:
         """The callable for ``venv.capture_steps(k, actions, after_step=...)`` of the env or either
         wrapper: its i-th call enqueues the collect of step i, reading ``actions[i]`` -- the static
         contiguous f32 [k, N, A] device buffer the captured steps read -- or, with ``actions=None``,
-        the env's own action buffer, which the in-graph random policy fills before every step."""
+        the env's own action buffer, which the in-graph random policy fills before every step.  A
+        contiguous f32 [N, A] buffer is read at every step: ``Actor.actions`` under
+        ``Actor.capture_rollout``, which the in-graph actor fills before every step."""
         base = self._base_env(venv)
         bufs = self._step_buffers(venv)
+        if torch.is_tensor(actions) and actions.dim() == 2:
+            if tuple(actions.shape) != (self.n_envs, self.action_dim) or actions.dtype != torch.float32 \
+                    or actions.device != self.device or not actions.is_contiguous():
+                raise ValueError(f"actions must be a contiguous f32 [{self.n_envs}, {self.action_dim}] tensor on "
+                                 f"{self.device}")
+
+            def enqueue_same() -> None:
+                self._launch_collect(actions, *bufs)
+
+            self._keep_graph = actions
+            return enqueue_same
         if actions is not None:
             if not torch.is_tensor(actions) or actions.dim() != 3 or \
                     tuple(actions.shape[1:]) != (self.n_envs, self.action_dim) or actions.dtype != torch.float32 \

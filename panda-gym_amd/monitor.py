@@ -269,6 +269,12 @@ class VecMonitor:
         self._mon.step(self._io)
         return out
 
+    def _enqueue_step(self, a: "torch.Tensor", what: str = "pgx_step") -> None:
+        """The wrapped object's step launches and the monitor's two, on the current stream (what
+        ``Actor.capture_rollout`` enqueues per step)."""
+        self.venv._enqueue_step(a, what)
+        self._enqueue_monitor()
+
     def capture_steps(self, k: int, actions: Optional["torch.Tensor"] = None, after_step=None):
         """The wrapped ``capture_steps`` with the monitor's launches behind every captured step.  The
         ring head, the step counter and the totals' parity are device words: any number of replays

@@ -255,9 +255,12 @@ class RolloutBuffer:
         """The callable for ``venv.capture_steps(k, actions, after_step=...)``: its i-th call
         enqueues the add of step i, reading ``actions[i]`` [N, A], ``values[i]`` and ``log_probs[i]``
         [N] (and ``terminal_values[i]``) -- static contiguous f32 device buffers [k, ...] the graph
-        reads at replay -- and the step outputs of ``venv`` as given."""
-        k, N = int(actions.shape[0]), self.n_envs
-        want = {"actions": (actions, (k, N, self.action_dim)), "values": (values, (k, N)),
+        reads at replay -- and the step outputs of ``venv`` as given.  ``actions`` may also be one
+        [N, A] buffer every step reads (``Actor.actions`` under ``Actor.capture_rollout``); ``k`` is then
+        ``values.shape[0]``."""
+        same = torch.is_tensor(actions) and actions.dim() == 2
+        k, N = int(values.shape[0] if same else actions.shape[0]), self.n_envs
+        want = {"actions": (actions, (N, self.action_dim) if same else (k, N, self.action_dim)), "values": (values, (k, N)),
                 "log_probs": (log_probs, (k, N))}
         if terminal_values is not None:
             want["terminal_values"] = (terminal_values, (k, N))
@@ -272,7 +275,7 @@ class RolloutBuffer:
             i = count[0]
             if i >= k:
                 raise IndexError(f"after_step: more than the {k} steps its buffers hold")
-            self._launch_add(actions[i], reward, values[i], log_probs[i],
+            self._launch_add(actions if same else actions[i], reward, values[i], log_probs[i],
                              None if terminal_values is None else terminal_values[i], obs, terminated, truncated)
             count[0] = i + 1
 
