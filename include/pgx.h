@@ -1058,6 +1058,125 @@ int pgx_actor_forward_host(const pgx_actor_config* cfg, const pgx_actor_weights*
                            const float* achieved_goal, const float* desired_goal, int32_t n, float* mean_out,
                            float* log_std_out);
 
+/* ----------------------------------------------------------------------
+ * ActorCritic: stable-baselines3's on-policy ActorCriticPolicy forward on the device
+ * (pgx_actor_critic.hip), as MultiInputPolicy instantiates it for these envs (PPO): one launch gives
+ * the action, the action clipped to the Box, V(obs) and the log-probability a RolloutBuffer stores; a
+ * second entry gives V(obs) alone (predict_values), optionally only for the env tiles a mask names.
+ *
+ * Features: as the Actor's, x = achieved_goal[3] | desired_goal[3] | observation[obs_dim].
+ * MlpExtractor: two separate trunks over x (SB3 >= 2.0 shares no layer): policy_net, n_pi_layers x
+ * (Linear + ReLU) of widths pi_hidden[l], and value_net, n_vf_layers x (Linear + ReLU) of widths
+ * vf_hidden[l]; 1..3 layers of 1..512 each, independently.  relu(v) = v > 0 ? v : +0.
+ * Heads: action_net Linear(last pi width -> action_dim) gives mean; value_net Linear(last vf width
+ * -> 1) gives value; log_std [action_dim] is a state-independent parameter (DiagGaussianDistribution).
+ *
+ * Arithmetic contract of every Linear: the Actor's, word for word (above): acc = bias[o], then
+ * acc = fmaf(x[k], W[o][k], acc) for k = 0 .. K16 - 1 ascending, K16 = K rounded up to 16 with +0
+ * padding, one accumulator per output, no split of K.  pgx_ac_forward_host restates it; the kernel's
+ * v_mfma_f32_16x16x4_f32 meets it bit for bit.
+ * Epilogue per env e and dimension d (f32, device expf; every operation rounded on its own, no
+ * contraction but the one fmaf written here):
+ *   std_d = expf(log_std[d])
+ *   a_d   = deterministic ? mean_d : fmaf(std_d, eps_d, mean_d)            -> action[e][d]
+ *           (SB3 stores the unclipped action)
+ *   c_d   = a_d < -1 ? -1 : a_d > 1 ? 1 : a_d                               -> clipped_action[e][d]
+ *           (collect_rollouts' np.clip to the Box: what the step reads)
+ *   z_d   = a_d - mean_d
+ *   lp_d  = ((-(z_d * z_d)) / (2 * (std_d * std_d)) - log_std[d]) - 0.9189385f
+ *           (torch Normal.log_prob's order; log_std itself stands for log(scale))
+ *   log_prob[e] = lp_0 + lp_1 + ... in ascending d
+ *   value[e]    = value_net's one output
+ * With deterministic != 0 log_prob is still written: the log-density of the mode, as SB3's
+ * forward(deterministic=True) returns.
+ *
+ * Noise eps [N, action_dim]: io.eps, or with io.eps NULL and deterministic == 0 the device
+ * Philox4x32-10 stream, defined as the Actor's but with the counter tag PGX_AC_PHILOX_TAG in place
+ * of 0x41435430 (an Actor and an ActorCritic of one seed draw different numbers) and a 64-bit step
+ * word of its own (pgx_ac_state), moved on by the same mechanism: the last workgroup to take a
+ * ticket, behind every workgroup's read, adds one.  A forward with io.eps or deterministic != 0
+ * leaves the word alone.
+ *
+ * pgx_ac_values: the value trunk and head alone; a computed value is bit for bit the forward's for
+ * the same observation.  `need` (device uint8 [N], or NULL: all): a workgroup's tile of 16 (or 32)
+ * consecutive envs none of which has need[e] != 0 runs no trunk and writes +0 for its envs; in every
+ * other tile all envs are written.  (The time-limit bootstrap: few tiles hold a truncated env.)
+ *
+ * Packed weights: the Actor's P[kb][tile][lane][i] per Linear; action_net in rows 0..6 of the policy
+ * head tile, value_net in row 0 of the value head tile.  One workgroup keeps the features in an LDS
+ * region of their own (row stride: the first layer's K16 + 4 floats) beside the two activation
+ * regions (row stride: the widest hidden layer's K16 + 4) and runs the policy trunk, then the value
+ * trunk; it owns 32 envs from 4096 envs on where the three regions fit 160 KB, else 16.
+ * ---------------------------------------------------------------------- */
+typedef struct pgx_ac* pgx_ac_handle;
+
+#define PGX_AC_PHILOX_TAG 0x50504F30u   /* counter word 3 of the noise stream, xor the dimension pair */
+
+typedef struct pgx_ac_config {
+    int32_t n_envs;
+    int32_t obs_dim;
+    int32_t action_dim;           /* 1..7 */
+    int32_t n_pi_layers;          /* 1..3 */
+    int32_t pi_hidden[3];         /* 1..512 each */
+    int32_t n_vf_layers;          /* 1..3 */
+    int32_t vf_hidden[3];         /* 1..512 each */
+    int32_t pad0;
+    uint64_t seed;                /* Philox key of the noise stream */
+} pgx_ac_config;
+
+/* torch-layout f32 parameters, device or host pointers: weight [out, in] row-major, bias [out]. */
+typedef struct pgx_ac_weights {
+    const float* pi_weight[3];
+    const float* pi_bias[3];
+    const float* vf_weight[3];
+    const float* vf_bias[3];
+    const float* action_net_weight;   /* [action_dim, last pi width] */
+    const float* action_net_bias;
+    const float* value_net_weight;    /* [1, last vf width] */
+    const float* value_net_bias;
+    const float* log_std;             /* [action_dim] */
+} pgx_ac_weights;
+
+/* Device pointers of one forward.  Only the non-NULL outputs and debug planes are written. */
+typedef struct pgx_ac_io {
+    const float* obs;             /* [N,obs_dim] */
+    const float* achieved_goal;   /* [N,3] */
+    const float* desired_goal;    /* [N,3] */
+    float* action;                /* [N,action_dim] or NULL */
+    float* clipped_action;        /* [N,action_dim] or NULL */
+    float* value;                 /* [N] or NULL */
+    float* log_prob;              /* [N] or NULL */
+    const float* eps;             /* [N,action_dim] or NULL: the device stream */
+    float* mean_out;              /* debug [N,action_dim] or NULL */
+    float* eps_out;               /* debug [N,action_dim] or NULL: the noise used (0 when deterministic) */
+    uint32_t* philox_out;         /* debug [N,4,4] or NULL: as pgx_actor_io's */
+} pgx_ac_io;
+
+/* PGX_E_INVALID, before any device call and naming the field, for n_envs <= 0, obs_dim <= 0 (or
+ * above 4096), action_dim outside 1..7, n_pi_layers / n_vf_layers outside 1..3, a pi_hidden /
+ * vf_hidden width outside 1..512, NULL cfg / out. */
+int pgx_ac_create(const pgx_ac_config* cfg, int device, pgx_ac_handle* out);
+void pgx_ac_destroy(pgx_ac_handle h);
+/* Packs the parameters into the handle's buffers on `stream`: a captured graph sees them at its next
+ * replay.  Device pointers are read where they lie, by kernel launches only; host pointers are first
+ * copied into the handle (copy operations on `stream`).  The sources must stay valid until the stream
+ * has run these.  pgx_ac_forward and pgx_ac_values are kernel launches only, whatever the arguments:
+ * no memcpy or memset node, no allocation, no sync. */
+int pgx_ac_set_weights(pgx_ac_handle h, const pgx_ac_weights* w, void* stream);
+/* One launch on `stream` (see above). */
+int pgx_ac_forward(pgx_ac_handle h, const pgx_ac_io* io, int32_t deterministic, void* stream);
+/* V(obs) into value_out [N], one launch on `stream`; need: device uint8 [N] or NULL (see above). */
+int pgx_ac_values(pgx_ac_handle h, const float* obs, const float* achieved_goal, const float* desired_goal,
+                  const uint8_t* need, float* value_out, void* stream);
+/* The noise step word after synchronising `stream`; set: synchronises, then writes it. */
+int pgx_ac_state(pgx_ac_handle h, uint64_t* step, void* stream);
+int pgx_ac_set_state(pgx_ac_handle h, uint64_t step, void* stream);
+/* The arithmetic contract in plain C++ on host arrays (std::fmaf), for n rows: mean [n, action_dim]
+ * and value [n] (either may be NULL).  cfg->n_envs is not read; w->log_std is not read.  Never
+ * touches a device; not a stepping path. */
+int pgx_ac_forward_host(const pgx_ac_config* cfg, const pgx_ac_weights* w, const float* obs, const float* achieved_goal,
+                        const float* desired_goal, int32_t n, float* mean_out, float* value_out);
+
 #ifdef __cplusplus
 }
 #endif

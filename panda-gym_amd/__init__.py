@@ -16,6 +16,7 @@ from .normalize import Normalizer, RunningMeanStd, VecNormalize
 from .monitor import EpisodeMonitor, VecMonitor, evaluate
 from .rollout import RolloutBuffer, RolloutBufferSamples
 from .actor import Actor
+from .actor_critic import ActorCritic
 from ._native import PgxError, load as load_native
 from .model import Model, load_model
 
@@ -24,4 +25,4 @@ __version__ = "0.1.0"
 __all__ = ["Box", "DictSpace", "PandaEnv", "PandaVecEnv", "make", "register_envs", "registered_ids",
            "seeded_goal", "seeded_reset", "spec", "task_draws", "pcg64_record", "pcg64_records", "pcg64_from_record", "PgxError", "load_native", "Model", "load_model",
            "HerReplayBuffer", "VecNormalize", "Normalizer", "RunningMeanStd",
-           "EpisodeMonitor", "VecMonitor", "evaluate", "RolloutBuffer", "RolloutBufferSamples", "Actor"]
+           "EpisodeMonitor", "VecMonitor", "evaluate", "RolloutBuffer", "RolloutBufferSamples", "Actor", "ActorCritic"]

@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 from .abi import PGX_E_INVALID  # noqa: F401 (re-exported for the C-ABI tests)
-from .abi import (PgxActorConfig, PgxActorIo, PgxActorWeights, PgxConfig, PgxMonitorConfig, PgxMonitorIo, PgxMonitorTotals, PgxNormConfig, PgxNormIo, PgxReplayBatch,
+from .abi import (PgxAcConfig, PgxAcIo, PgxAcWeights, PgxActorConfig, PgxActorIo, PgxActorWeights, PgxConfig, PgxMonitorConfig, PgxMonitorIo, PgxMonitorTotals, PgxNormConfig, PgxNormIo, PgxReplayBatch,
                   PgxReplayConfig, PgxReplayStep, PgxReplayViews, PgxRolloutBatch, PgxRolloutConfig, PgxRolloutIo,
                   PgxRolloutViews, PgxStateView, PgxStepOut, PgxTransition)
 
@@ -33,6 +33,8 @@ EXPORTS = [
     "pgx_rollout_set_last", "pgx_rollout_state", "pgx_rollout_arrays",
     "pgx_actor_create", "pgx_actor_destroy", "pgx_actor_set_weights", "pgx_actor_forward", "pgx_actor_state",
     "pgx_actor_set_state", "pgx_actor_forward_host",
+    "pgx_ac_create", "pgx_ac_destroy", "pgx_ac_set_weights", "pgx_ac_forward", "pgx_ac_values", "pgx_ac_state",
+    "pgx_ac_set_state", "pgx_ac_forward_host",
 ]
 
 
@@ -140,6 +142,16 @@ def load(path: str = None):
     lib.pgx_actor_set_state.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
     lib.pgx_actor_forward_host.argtypes = [C.POINTER(PgxActorConfig), C.POINTER(PgxActorWeights), C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.pgx_ac_create.argtypes = [C.POINTER(PgxAcConfig), C.c_int, C.POINTER(C.c_void_p)]
+    lib.pgx_ac_destroy.argtypes = [C.c_void_p]
+    lib.pgx_ac_destroy.restype = None
+    lib.pgx_ac_set_weights.argtypes = [C.c_void_p, C.POINTER(PgxAcWeights), C.c_void_p]
+    lib.pgx_ac_forward.argtypes = [C.c_void_p, C.POINTER(PgxAcIo), C.c_int32, C.c_void_p]
+    lib.pgx_ac_values.argtypes = [C.c_void_p] * 7
+    lib.pgx_ac_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
+    lib.pgx_ac_set_state.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.pgx_ac_forward_host.argtypes = [C.POINTER(PgxAcConfig), C.POINTER(PgxAcWeights), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     _libs[path] = lib
     return lib
 

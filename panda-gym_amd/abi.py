@@ -283,6 +283,34 @@ class PgxActorIo(C.Structure):
     ]
 
 
+# ActorCritic (include/pgx.h, pgx_ac_*)
+AC_PHILOX_TAG = 0x50504F30   # PGX_AC_PHILOX_TAG: the noise stream's counter word 3 (not the Actor's)
+
+
+class PgxAcConfig(C.Structure):
+    _fields_ = [
+        ("n_envs", C.c_int32), ("obs_dim", C.c_int32), ("action_dim", C.c_int32), ("n_pi_layers", C.c_int32),
+        ("pi_hidden", C.c_int32 * 3), ("n_vf_layers", C.c_int32), ("vf_hidden", C.c_int32 * 3), ("pad0", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
+class PgxAcWeights(C.Structure):
+    _fields_ = [
+        ("pi_weight", C.c_void_p * 3), ("pi_bias", C.c_void_p * 3), ("vf_weight", C.c_void_p * 3),
+        ("vf_bias", C.c_void_p * 3), ("action_net_weight", C.c_void_p), ("action_net_bias", C.c_void_p),
+        ("value_net_weight", C.c_void_p), ("value_net_bias", C.c_void_p), ("log_std", C.c_void_p),
+    ]
+
+
+class PgxAcIo(C.Structure):
+    _fields_ = [
+        ("obs", C.c_void_p), ("achieved_goal", C.c_void_p), ("desired_goal", C.c_void_p), ("action", C.c_void_p),
+        ("clipped_action", C.c_void_p), ("value", C.c_void_p), ("log_prob", C.c_void_p), ("eps", C.c_void_p),
+        ("mean_out", C.c_void_p), ("eps_out", C.c_void_p), ("philox_out", C.c_void_p),
+    ]
+
+
 def rollout_row_fields(obs_dim: int, action_dim: int):
     """(name, offset, width) of the RolloutBuffer batch row layout of include/pgx.h, plus row_dim."""
     f, o = [], 0
