@@ -1177,6 +1177,111 @@ int pgx_ac_set_state(pgx_ac_handle h, uint64_t step, void* stream);
 int pgx_ac_forward_host(const pgx_ac_config* cfg, const pgx_ac_weights* w, const float* obs, const float* achieved_goal,
                         const float* desired_goal, int32_t n, float* mean_out, float* value_out);
 
+/* ----------------------------------------------------------------------
+ * SdeActor: stable-baselines3's off-policy actor built with use_sde=True (sac/policies.py Actor;
+ * sb3_contrib's TQC actor is the same class body), full_std=True, use_expln=False, latent_sde =
+ * latent_pi: generalised state-dependent exploration on the device (pgx_sde_actor.hip).  Each env
+ * holds an exploration matrix E[e] [H, A], resampled by pgx_sde_actor_reset_noise; between two
+ * resets the noise is a fixed function of the state.
+ *
+ * Features and trunk: the Actor's, word for word (above): x = achieved_goal[3] | desired_goal[3] |
+ * observation[obs_dim]; n_layers x (Linear + ReLU), widths hidden[l] in 1..512, every Linear output
+ *   acc = bias[o];  for k = 0 .. K16 - 1 ascending:  acc = fmaf(x[k], W[o][k], acc)
+ * with K16 = K rounded up to 16 (+0 padding), one accumulator per output.  latent[e][0..H) is the
+ * last hidden activation, H = hidden[n_layers - 1].
+ *   mean    = the mu Linear on that same chain over latent; with clip_mean > 0: mean < -clip_mean ?
+ *             -clip_mean : mean > clip_mean ? clip_mean : mean (Hardtanh; SB3's default 2.0).  There
+ *             is no log_std head and no [-20, 2] clamp: SB3's gSDE path has neither.
+ *   std[h][a] = expf(log_std[h][a]), log_std a parameter [H, A]; computed by a kernel at
+ *             pgx_sde_actor_set_weights and kept in the handle (pgx_sde_actor_get_std).
+ *   noise[e][a]: ONE chain and nothing else,
+ *             acc = +0;  for h = 0 .. H - 1 ascending:  acc = fmaf(latent[e][h], E[e][h][a], acc)
+ *             (exactly H terms: no padding, no split into sub-chains, no reassociation).
+ *   action  = tanhf(deterministic ? mean : mean + noise): one f32 add, device tanhf.  A
+ *             deterministic forward reads no matrix.
+ *
+ * pgx_sde_actor_reset_noise resamples every env's matrix in one launch (SB3 sample_weights(log_std,
+ * batch_size = n_envs): Normal(0, std).rsample() = eps * std).  `generation` is a 64-bit device word
+ * (pgx_sde_actor_state); for env e, flat index j = h * A + a and block q = j / 4 (q < 1024):
+ *   r = philox4x32_10(counter = (gen lo, gen hi, e, PGX_SDE_PHILOX_TAG ^ q), key = (seed lo, seed hi))
+ *   (r[0], r[1]) through the Actor's Box-Muller lines (above) give eps[4 q], eps[4 q + 1];
+ *   (r[2], r[3]) through the same lines give eps[4 q + 2], eps[4 q + 3];
+ *   E[e][h][a] = eps[j] * std[h][a], one f32 multiply.
+ * The counters are disjoint from the Actor's (0x41435430 ^ p) and the ActorCritic's (0x50504F30 ^ p).
+ * The last workgroup of the launch to take a ticket, behind every workgroup's read of the word, adds
+ * one to `generation`: every replay of a captured graph draws new matrices.  A forward never touches
+ * the word or a matrix.
+ *
+ * The handle stores the matrices in a layout of its own (one 16-byte load per lane gives four
+ * consecutive h of one (env, a), and a wave's loads are contiguous):
+ *   S[e / 16][h / 4][e % 16][a][h % 4], H rounded up to 4 and n_envs to 16, padding kept at +0;
+ * pgx_sde_actor_get_matrices / _set_matrices translate from and to SB3's [N, H, A] with a kernel.
+ * Every entry below but create / destroy / state / set_state enqueues kernel launches only on the
+ * caller's stream (no memcpy or memset node, no allocation, no sync), so everything captures;
+ * pgx_sde_actor_set_weights first copies the parameters into the handle (copy operations on `stream`).
+ * ---------------------------------------------------------------------- */
+typedef struct pgx_sde_actor* pgx_sde_actor_handle;
+
+#define PGX_SDE_PHILOX_TAG 0x53444500u   /* counter word 3 of the matrix draw, xor the block q */
+
+typedef struct pgx_sde_actor_config {
+    int32_t n_envs;
+    int32_t obs_dim;
+    int32_t action_dim;           /* 1..7 */
+    int32_t n_layers;             /* 1..3 hidden layers */
+    int32_t hidden[3];            /* widths of the first n_layers, 1..512 each */
+    int32_t pad0;
+    double clip_mean;             /* >= 0; 0: off */
+    uint64_t seed;                /* Philox key of the matrix draw */
+} pgx_sde_actor_config;
+
+/* torch-layout f32 parameters, device or host pointers: weight[l] [out, in] row-major and bias[l]
+ * [out] for the hidden layers l < n_layers, then mu at index n_layers; log_std [H, action_dim]. */
+typedef struct pgx_sde_actor_weights {
+    const float* weight[4];
+    const float* bias[4];
+    const float* log_std;
+} pgx_sde_actor_weights;
+
+/* Device pointers of one forward.  Only `action` and the non-NULL debug planes are written. */
+typedef struct pgx_sde_actor_io {
+    const float* obs;             /* [N,obs_dim] */
+    const float* achieved_goal;   /* [N,3] */
+    const float* desired_goal;    /* [N,3] */
+    float* action;                /* [N,action_dim] */
+    float* mean_out;              /* debug [N,action_dim] or NULL: mean (after clip_mean) */
+    float* latent_out;            /* debug [N,H] or NULL */
+    float* noise_out;             /* debug [N,action_dim] or NULL: the noise chain (+0 when deterministic) */
+} pgx_sde_actor_io;
+
+/* PGX_E_INVALID, before any device call and naming the field, for n_envs <= 0, obs_dim <= 0 (or
+ * above 4096), action_dim outside 1..7, n_layers outside 1..3, a hidden width outside 1..512, a
+ * negative or non-finite clip_mean, NULL cfg / out.  The matrices (+0) and std (+0) are allocated here. */
+int pgx_sde_actor_create(const pgx_sde_actor_config* cfg, int device, pgx_sde_actor_handle* out);
+void pgx_sde_actor_destroy(pgx_sde_actor_handle h);
+/* Copies the parameters into the handle, packs them and computes std there, on `stream`: a captured
+ * graph sees them at its next replay.  The sources must stay valid until the stream has run the copies. */
+int pgx_sde_actor_set_weights(pgx_sde_actor_handle h, const pgx_sde_actor_weights* w, void* stream);
+/* One launch: every env's matrix from `generation`, which it moves on by one (see above).  Debug planes
+ * (device, or NULL): eps_out [N, H, A] f32, philox_out [N, 4, 4] u32 (r[0..3] of the blocks q < 4). */
+int pgx_sde_actor_reset_noise(pgx_sde_actor_handle h, float* eps_out, uint32_t* philox_out, void* stream);
+/* One launch (see above). */
+int pgx_sde_actor_forward(pgx_sde_actor_handle h, const pgx_sde_actor_io* io, int32_t deterministic, void* stream);
+/* The generation word after synchronising `stream`; set: synchronises, then writes it. */
+int pgx_sde_actor_state(pgx_sde_actor_handle h, uint64_t* generation, void* stream);
+int pgx_sde_actor_set_state(pgx_sde_actor_handle h, uint64_t generation, void* stream);
+/* The matrices as SB3 lays them out, device f32 [N, H, A]: one launch each on `stream`. */
+int pgx_sde_actor_get_matrices(pgx_sde_actor_handle h, float* out, void* stream);
+int pgx_sde_actor_set_matrices(pgx_sde_actor_handle h, const float* in, void* stream);
+/* std into device f32 [H, A]: one launch on `stream`. */
+int pgx_sde_actor_get_std(pgx_sde_actor_handle h, float* out, void* stream);
+/* The arithmetic contract above in plain C++ on host arrays (std::fmaf), for n rows with their
+ * matrices [n, H, A]: mean [n, action_dim], latent [n, H], noise [n, action_dim] (each may be NULL).
+ * cfg->n_envs, cfg->seed and w->log_std are not read.  Never touches a device; not a stepping path. */
+int pgx_sde_actor_forward_host(const pgx_sde_actor_config* cfg, const pgx_sde_actor_weights* w, const float* obs,
+                               const float* achieved_goal, const float* desired_goal, const float* matrices, int32_t n,
+                               float* mean_out, float* latent_out, float* noise_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ from .monitor import EpisodeMonitor, VecMonitor, evaluate
 from .rollout import RolloutBuffer, RolloutBufferSamples
 from .actor import Actor
 from .actor_critic import ActorCritic
+from .sde_actor import SdeActor
 from ._native import PgxError, load as load_native
 from .model import Model, load_model
 
@@ -25,4 +26,5 @@ __version__ = "0.1.0"
 __all__ = ["Box", "DictSpace", "PandaEnv", "PandaVecEnv", "make", "register_envs", "registered_ids",
            "seeded_goal", "seeded_reset", "spec", "task_draws", "pcg64_record", "pcg64_records", "pcg64_from_record", "PgxError", "load_native", "Model", "load_model",
            "HerReplayBuffer", "VecNormalize", "Normalizer", "RunningMeanStd",
-           "EpisodeMonitor", "VecMonitor", "evaluate", "RolloutBuffer", "RolloutBufferSamples", "Actor", "ActorCritic"]
+           "EpisodeMonitor", "VecMonitor", "evaluate", "RolloutBuffer", "RolloutBufferSamples", "Actor", "ActorCritic",
+           "SdeActor"]

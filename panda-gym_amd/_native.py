@@ -11,7 +11,8 @@ import os
 from .abi import PGX_E_INVALID  # noqa: F401 (re-exported for the C-ABI tests)
 from .abi import (PgxAcConfig, PgxAcIo, PgxAcWeights, PgxActorConfig, PgxActorIo, PgxActorWeights, PgxConfig, PgxMonitorConfig, PgxMonitorIo, PgxMonitorTotals, PgxNormConfig, PgxNormIo, PgxReplayBatch,
                   PgxReplayConfig, PgxReplayStep, PgxReplayViews, PgxRolloutBatch, PgxRolloutConfig, PgxRolloutIo,
-                  PgxRolloutViews, PgxStateView, PgxStepOut, PgxTransition)
+                  PgxRolloutViews, PgxSdeActorConfig, PgxSdeActorIo, PgxSdeActorWeights, PgxStateView, PgxStepOut,
+                  PgxTransition)
 
 LIB_PATH = os.environ.get("PGX_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpgx.so")
 
@@ -35,6 +36,9 @@ EXPORTS = [
     "pgx_actor_set_state", "pgx_actor_forward_host",
     "pgx_ac_create", "pgx_ac_destroy", "pgx_ac_set_weights", "pgx_ac_forward", "pgx_ac_values", "pgx_ac_state",
     "pgx_ac_set_state", "pgx_ac_forward_host",
+    "pgx_sde_actor_create", "pgx_sde_actor_destroy", "pgx_sde_actor_set_weights", "pgx_sde_actor_reset_noise",
+    "pgx_sde_actor_forward", "pgx_sde_actor_state", "pgx_sde_actor_set_state", "pgx_sde_actor_get_matrices",
+    "pgx_sde_actor_set_matrices", "pgx_sde_actor_get_std", "pgx_sde_actor_forward_host",
 ]
 
 
@@ -152,6 +156,19 @@ def load(path: str = None):
     lib.pgx_ac_set_state.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
     lib.pgx_ac_forward_host.argtypes = [C.POINTER(PgxAcConfig), C.POINTER(PgxAcWeights), C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.pgx_sde_actor_create.argtypes = [C.POINTER(PgxSdeActorConfig), C.c_int, C.POINTER(C.c_void_p)]
+    lib.pgx_sde_actor_destroy.argtypes = [C.c_void_p]
+    lib.pgx_sde_actor_destroy.restype = None
+    lib.pgx_sde_actor_set_weights.argtypes = [C.c_void_p, C.POINTER(PgxSdeActorWeights), C.c_void_p]
+    lib.pgx_sde_actor_reset_noise.argtypes = [C.c_void_p] * 4
+    lib.pgx_sde_actor_forward.argtypes = [C.c_void_p, C.POINTER(PgxSdeActorIo), C.c_int32, C.c_void_p]
+    lib.pgx_sde_actor_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
+    lib.pgx_sde_actor_set_state.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.pgx_sde_actor_get_matrices.argtypes = [C.c_void_p] * 3
+    lib.pgx_sde_actor_set_matrices.argtypes = [C.c_void_p] * 3
+    lib.pgx_sde_actor_get_std.argtypes = [C.c_void_p] * 3
+    lib.pgx_sde_actor_forward_host.argtypes = [C.POINTER(PgxSdeActorConfig), C.POINTER(PgxSdeActorWeights)] + \
+        [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3
     _libs[path] = lib
     return lib
 

@@ -283,6 +283,28 @@ class PgxActorIo(C.Structure):
     ]
 
 
+# SdeActor (include/pgx.h, pgx_sde_actor_*)
+SDE_PHILOX_TAG = 0x53444500   # PGX_SDE_PHILOX_TAG: counter word 3 of the matrix draw, xor the block q
+
+
+class PgxSdeActorConfig(C.Structure):
+    _fields_ = [
+        ("n_envs", C.c_int32), ("obs_dim", C.c_int32), ("action_dim", C.c_int32), ("n_layers", C.c_int32),
+        ("hidden", C.c_int32 * 3), ("pad0", C.c_int32), ("clip_mean", C.c_double), ("seed", C.c_uint64),
+    ]
+
+
+class PgxSdeActorWeights(C.Structure):
+    _fields_ = [("weight", C.c_void_p * 4), ("bias", C.c_void_p * 4), ("log_std", C.c_void_p)]
+
+
+class PgxSdeActorIo(C.Structure):
+    _fields_ = [
+        ("obs", C.c_void_p), ("achieved_goal", C.c_void_p), ("desired_goal", C.c_void_p), ("action", C.c_void_p),
+        ("mean_out", C.c_void_p), ("latent_out", C.c_void_p), ("noise_out", C.c_void_p),
+    ]
+
+
 # ActorCritic (include/pgx.h, pgx_ac_*)
 AC_PHILOX_TAG = 0x50504F30   # PGX_AC_PHILOX_TAG: the noise stream's counter word 3 (not the Actor's)
 

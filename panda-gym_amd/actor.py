@@ -11,8 +11,8 @@ of an env or a wrapper and writes the action buffer the next step reads, so ``ca
 ``device="cpu"`` an ``Actor`` only holds and maps parameters (``load_state_dict`` / ``state_dict`` /
 ``forward_host``, the host model of the kernel's arithmetic, which is a test oracle and not a way to step).
 
-PPO's actor-critic lives next door (actor_critic.py).  Critics for SAC / TQC, optimisers and gSDE
-exploration are not here.
+PPO's actor-critic lives next door (actor_critic.py), the gSDE actor (``use_sde=True``, per-env exploration
+matrices) in sde_actor.py.  Critics for SAC / TQC and optimisers are not here.
 """
 from __future__ import annotations
 

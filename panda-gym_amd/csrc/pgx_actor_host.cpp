@@ -174,3 +174,77 @@ extern "C" int pgx_ac_forward_host(const pgx_ac_config* cfg, const pgx_ac_weight
     }
     return PGX_OK;
 }
+
+/* ---------------------------------------------------------------- SdeActor (include/pgx.h) */
+
+/* pgx_sde_actor_create's checks (no device call); `what` names the entry point */
+int pgx_sde_actor_check_config(const pgx_sde_actor_config* c, const char* what, bool with_envs) {
+    char msg[160];
+    auto bad = [&](const char* field) {
+        snprintf(msg, sizeof(msg), "%s: %s", what, field);
+        return pgx_set_error(PGX_E_INVALID, msg);
+    };
+    if (!c) return bad("null config");
+    if (with_envs && c->n_envs <= 0) return bad("n_envs must be > 0");
+    if (c->obs_dim <= 0 || c->obs_dim > 4096) return bad("obs_dim must be in 1..4096");
+    if (c->action_dim < 1 || c->action_dim > PGX_ACTOR_MAX_ACTION) return bad("action_dim must be in 1..7");
+    if (c->n_layers < 1 || c->n_layers > PGX_ACTOR_MAX_LAYERS) return bad("n_layers must be in 1..3");
+    for (int l = 0; l < c->n_layers; l++)
+        if (c->hidden[l] < 1 || c->hidden[l] > PGX_ACTOR_MAX_WIDTH) return bad("hidden widths must be in 1..512");
+    if (!(c->clip_mean >= 0.0) || std::isinf(c->clip_mean)) return bad("clip_mean must be finite and >= 0");
+    return PGX_OK;
+}
+
+extern "C" int pgx_sde_actor_forward_host(const pgx_sde_actor_config* cfg, const pgx_sde_actor_weights* w,
+                                          const float* obs, const float* achieved_goal, const float* desired_goal,
+                                          const float* matrices, int32_t n, float* mean_out, float* latent_out,
+                                          float* noise_out) {
+    const char* what = "pgx_sde_actor_forward_host";
+    const int rc = pgx_sde_actor_check_config(cfg, what, false);
+    if (rc != PGX_OK) return rc;
+    if (!w || !obs || !achieved_goal || !desired_goal || n < 0)
+        return pgx_set_error(PGX_E_INVALID, "pgx_sde_actor_forward_host: null pointer or n < 0");
+    if (noise_out && !matrices)
+        return pgx_set_error(PGX_E_INVALID, "pgx_sde_actor_forward_host: null matrices with noise_out");
+    const int nl = cfg->n_layers, A = cfg->action_dim, od = cfg->obs_dim, H = cfg->hidden[nl - 1];
+    for (int l = 0; l <= nl; l++)
+        if (!w->weight[l] || !w->bias[l])
+            return pgx_set_error(PGX_E_INVALID, "pgx_sde_actor_forward_host: null weight or bias pointer");
+    const float clip = (float)cfg->clip_mean;
+    std::vector<float> x(od + 6), y(PGX_ACTOR_MAX_WIDTH), z(PGX_ACTOR_MAX_WIDTH);
+    for (int32_t e = 0; e < n; e++) {
+        for (int k = 0; k < 3; k++) x[k] = achieved_goal[(size_t)e * 3 + k];
+        for (int k = 0; k < 3; k++) x[3 + k] = desired_goal[(size_t)e * 3 + k];
+        for (int k = 0; k < od; k++) x[6 + k] = obs[(size_t)e * od + k];
+        const float* in = x.data();
+        int K = od + 6;
+        float* out = y.data();
+        for (int l = 0; l < nl; l++) {
+            linear(w->weight[l], w->bias[l], in, K, cfg->hidden[l], true, out);
+            in = out;
+            K = cfg->hidden[l];
+            out = out == y.data() ? z.data() : y.data();
+        }
+        const float* latent = in;
+        if (latent_out)
+            for (int h = 0; h < H; h++) latent_out[(size_t)e * H + h] = latent[h];
+        if (mean_out) {
+            float head[PGX_ACTOR_MAX_ACTION];
+            linear(w->weight[nl], w->bias[nl], latent, H, A, false, head);
+            for (int d = 0; d < A; d++) {
+                float m = head[d];
+                if (clip > 0.0f) m = m < -clip ? -clip : (m > clip ? clip : m);
+                mean_out[(size_t)e * A + d] = m;
+            }
+        }
+        if (noise_out) {
+            const float* E = matrices + (size_t)e * H * A;
+            for (int d = 0; d < A; d++) {
+                float acc = 0.0f;   /* one chain, exactly H terms */
+                for (int h = 0; h < H; h++) acc = std::fmaf(latent[h], E[(size_t)h * A + d], acc);
+                noise_out[(size_t)e * A + d] = acc;
+            }
+        }
+    }
+    return PGX_OK;
+}

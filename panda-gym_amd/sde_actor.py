@@ -1,0 +1,324 @@
+"""Device-resident gSDE actor: stable-baselines3's off-policy actor built with ``use_sde=True``.
+
+The reference trains TQC by default (train_config.py) with ``use_sde=True``, ``log_std_init=-3`` and
+``net_arch`` [256, 256] / [400, 300] (hyperparameters.py): every rollout it collects explores with
+generalised state-dependent exploration.  Each env holds an exploration matrix ``E`` [H, A], drawn at
+``reset_noise``; an action is ``tanh(mean + latent @ E)``, so between two resamples the noise is a fixed
+function of the state.  ``SdeActor`` is that forward -- CombinedExtractor's concatenation, the Linear +
+ReLU trunk, ``mu`` with its ``clip_mean`` Hardtanh, the per-env mat-vec and the squash -- and the
+resampling, in libpgx.so (pgx_sde_actor.hip; C-ABI and the arithmetic contract in include/pgx.h, section
+"SdeActor").  Both are kernel launches only and the draw's generation word lives on the device, so
+``capture_rollout`` puts resample, observe, act, step, collect into one graph whose every replay draws
+new matrices.  ``full_std=True``, ``use_expln=False`` and ``latent_sde = latent_pi`` (SB3's defaults) are
+what is built.  No CPU fallback: with ``device="cpu"`` an ``SdeActor`` only holds and maps parameters
+(``load_state_dict`` / ``state_dict`` / ``forward_host``, the host model of the kernel's arithmetic).
+
+The distribution's variance and ``log_prob``, critics and optimisers are training-side and not here.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Any, Callable, Dict, List, Optional, Sequence
+
+import numpy as np
+
+from . import abi
+from ._native import PgxError, check, load
+from .actor import OBS_KEYS
+
+try:
+    import torch
+except ImportError:  # pragma: no cover
+    torch = None
+
+
+class SdeActor:
+    """SB3's SAC / TQC actor with ``use_sde=True`` on the device.
+
+    ``env``: a ``PandaVecEnv`` or a wrapper of one (``n_envs``, the dims and the device are read from it),
+    or pass ``obs_dim``, ``action_dim`` and ``n_envs``.  ``net_arch``: 1 to 3 hidden widths of 1 to 512;
+    the last one is the latent width H.  ``log_std_init``: the fill of the ``log_std`` parameter [H, A].
+    ``clip_mean`` > 0: the Hardtanh on the mean.  The weights are zero and the exploration matrices are
+    zero until ``load_state_dict`` and ``reset_noise``."""
+
+    def __init__(self, env: Any = None, obs_dim: Optional[int] = None, action_dim: Optional[int] = None,
+                 net_arch: Sequence[int] = (256, 256), log_std_init: float = -3.0, clip_mean: float = 2.0,
+                 full_std: bool = True, use_expln: bool = False, seed: int = 0, device: Any = None,
+                 n_envs: Optional[int] = None):
+        if torch is None:
+            raise PgxError("SdeActor needs torch for its buffers")
+        if not full_std:
+            raise ValueError("full_std=False is not built")
+        if use_expln:
+            raise ValueError("use_expln=True is not built")
+        if env is not None:
+            n_envs = env.num_envs
+            obs_dim = env.obs_dim if obs_dim is None else obs_dim
+            action_dim = env.action_dim if action_dim is None else action_dim
+            device = env.device if device is None else device
+        if obs_dim is None or action_dim is None or n_envs is None:
+            raise ValueError("pass env, or obs_dim, action_dim and n_envs")
+        if int(n_envs) <= 0:
+            raise ValueError("n_envs must be > 0")
+        self.lib = load()
+        self.device = torch.device("cuda:0" if device is None else device)
+        self.n_envs, self.obs_dim, self.action_dim = int(n_envs), int(obs_dim), int(action_dim)
+        self.net_arch = tuple(int(w) for w in net_arch)
+        self.log_std_init, self.clip_mean, self.seed = float(log_std_init), float(clip_mean), int(seed)
+        cfg = abi.PgxSdeActorConfig()
+        cfg.n_envs, cfg.obs_dim, cfg.action_dim = self.n_envs, self.obs_dim, self.action_dim
+        cfg.n_layers = len(self.net_arch)
+        for i, w in enumerate(self.net_arch[:abi.ACTOR_MAX_LAYERS]):
+            cfg.hidden[i] = w
+        cfg.clip_mean = self.clip_mean
+        cfg.seed = self.seed & 0xFFFFFFFFFFFFFFFF
+        self._cfg = cfg
+        self._h = None
+        self.latent_dim = self.net_arch[min(len(self.net_arch), abi.ACTOR_MAX_LAYERS) - 1] if self.net_arch else 0
+        # the parameters as given (torch layout), on the actor's device: what set_weights reads
+        dims = [self.obs_dim + 6] + list(self.net_arch)
+        shapes = [(dims[i + 1], dims[i]) for i in range(len(self.net_arch))] + [(self.action_dim, dims[-1])]
+        # sac/policies.py Actor: latent_pi = Sequential(Linear, ReLU, ...); mu = Sequential(Linear, Hardtanh)
+        # when clip_mean > 0, a bare Linear otherwise; log_std a bare parameter
+        self._names = [f"latent_pi.{2 * i}" for i in range(len(self.net_arch))] + ["mu.0" if self.clip_mean > 0 else "mu"]
+        self._w = [torch.zeros(s, dtype=torch.float32, device=self.device) for s in shapes]
+        self._b = [torch.zeros(s[0], dtype=torch.float32, device=self.device) for s in shapes]
+        self._log_std = torch.full((max(self.latent_dim, 0), self.action_dim), self.log_std_init, dtype=torch.float32,
+                                   device=self.device)
+        self.actions = torch.zeros((self.n_envs, self.action_dim), dtype=torch.float32, device=self.device)
+        self._debug: Optional[Dict[str, "torch.Tensor"]] = None
+        self._keep: List[Any] = []
+        if self.device.type == "cuda":
+            h = C.c_void_p()
+            torch.cuda.set_device(self.device)
+            check(self.lib.pgx_sde_actor_create(C.byref(cfg), self.device.index or 0, C.byref(h)), "pgx_sde_actor_create",
+                  self.lib)
+            self._h = h
+            self._push()
+        else:   # the library's argument checks either way: the host model on no rows
+            self.forward_host({"observation": np.zeros((0, self.obs_dim), np.float32),
+                               "achieved_goal": np.zeros((0, 3), np.float32), "desired_goal": np.zeros((0, 3), np.float32)},
+                              np.zeros((0, max(self.latent_dim, 0), self.action_dim), np.float32))
+
+    # ------------------------------------------------------------ plumbing
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _need_device(self):
+        if self._h is None:
+            raise PgxError("this SdeActor has no device handle (device='cpu' or closed): no CPU fallback")
+
+    def _weights_struct(self, ws, bs, log_std) -> abi.PgxSdeActorWeights:
+        w = abi.PgxSdeActorWeights()
+        for i, (x, y) in enumerate(zip(ws[:4], bs[:4])):   # (more: the library rejects n_layers)
+            w.weight[i], w.bias[i] = x, y
+        w.log_std = log_std
+        return w
+
+    def _push(self) -> None:
+        w = self._weights_struct([t.data_ptr() for t in self._w], [t.data_ptr() for t in self._b], self._log_std.data_ptr())
+        check(self.lib.pgx_sde_actor_set_weights(self._h, C.byref(w), self._stream()), "pgx_sde_actor_set_weights", self.lib)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            torch.cuda.synchronize(self.device)
+            self.lib.pgx_sde_actor_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ----------------------------------------------------------- parameters
+    def _slots(self):
+        """(key, tensor) of every parameter in SB3's order."""
+        out = []
+        for name, w, b in zip(self._names, self._w, self._b):
+            out += [(f"{name}.weight", w), (f"{name}.bias", b)]
+        return out + [("log_std", self._log_std)]
+
+    def state_dict(self) -> Dict[str, "torch.Tensor"]:
+        """The parameters under SB3's actor key names (copies, on the actor's device)."""
+        return {k: t.clone() for k, t in self._slots()}
+
+    def load_state_dict(self, sd: Dict[str, Any]) -> None:
+        """Load SB3 gSDE actor parameters: ``latent_pi.{0,2,4}``, ``mu.0`` (``mu`` with ``clip_mean == 0``),
+        ``.weight`` [out, in] and ``.bias`` [out], and ``log_std`` [H, A]; a policy's state dict works too
+        (its ``actor.`` keys are read, the rest ignored).  The packed weights and ``std`` in the handle are
+        replaced on the current stream: a captured graph uses them at its next replay."""
+        if any(k.startswith("actor.") for k in sd):
+            sd = {k[len("actor."):]: v for k, v in sd.items() if k.startswith("actor.")}
+        new = []
+        for key, cur in self._slots():
+            if key not in sd:
+                raise KeyError(f"load_state_dict: missing key {key!r}")
+            v = sd[key]
+            t = v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
+            if tuple(t.shape) != tuple(cur.shape):
+                raise ValueError(f"load_state_dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(cur.shape)}")
+            new.append(t.to(device=self.device, dtype=torch.float32).contiguous())
+        for (_, cur), t in zip(self._slots(), new):
+            cur.copy_(t)   # in place: the handle's copies read these same buffers
+        if self._h is not None:
+            self._push()
+
+    @property
+    def std(self) -> "torch.Tensor":
+        """``exp(log_std)`` [H, A] as the handle holds it (a copy)."""
+        self._need_device()
+        out = torch.empty_like(self._log_std)
+        check(self.lib.pgx_sde_actor_get_std(self._h, C.c_void_p(out.data_ptr()), self._stream()), "pgx_sde_actor_get_std",
+              self.lib)
+        return out
+
+    # ----------------------------------------------------------------- noise
+    def enable_debug(self) -> Dict[str, "torch.Tensor"]:
+        """Allocate the debug planes every later call fills: of a forward ``mean`` [N, A] (after
+        ``clip_mean``), ``latent`` [N, H] and ``noise`` [N, A]; of a ``reset_noise`` ``eps`` [N, H, A] f32
+        and ``philox`` [N, 4, 4] int32 (the words of the blocks q < 4).  Tests and tools only."""
+        if self._debug is None:
+            z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=self.device)  # noqa: E731
+            N, A, H = self.n_envs, self.action_dim, self.latent_dim
+            self._debug = {"mean": z(N, A), "latent": z(N, H), "noise": z(N, A), "eps": z(N, H, A),
+                           "philox": z(N, 4, 4, dt=torch.int32)}
+        return self._debug
+
+    def reset_noise(self) -> None:
+        """Resample every env's exploration matrix (SB3 ``reset_noise(n_envs)``): one launch, which moves
+        ``noise_generation`` on by one."""
+        self._need_device()
+        d = self._debug
+        e, p = (None, None) if d is None else (C.c_void_p(d["eps"].data_ptr()), C.c_void_p(d["philox"].data_ptr()))
+        check(self.lib.pgx_sde_actor_reset_noise(self._h, e, p, self._stream()), "pgx_sde_actor_reset_noise", self.lib)
+
+    @property
+    def noise_generation(self) -> int:
+        """The device word that keys the matrix draw and counts the resamples (this synchronises).  Setting
+        it back reproduces the draws."""
+        self._need_device()
+        v = C.c_uint64(0)
+        check(self.lib.pgx_sde_actor_state(self._h, C.byref(v), self._stream()), "pgx_sde_actor_state", self.lib)
+        return int(v.value)
+
+    @noise_generation.setter
+    def noise_generation(self, value: int) -> None:
+        self._need_device()
+        check(self.lib.pgx_sde_actor_set_state(self._h, C.c_uint64(int(value) & 0xFFFFFFFFFFFFFFFF), self._stream()),
+              "pgx_sde_actor_set_state", self.lib)
+
+    @property
+    def exploration_matrices(self) -> "torch.Tensor":
+        """The matrices [N, H, A] in SB3's layout (a copy; the handle keeps a layout of its own)."""
+        self._need_device()
+        out = torch.empty((self.n_envs, self.latent_dim, self.action_dim), dtype=torch.float32, device=self.device)
+        check(self.lib.pgx_sde_actor_get_matrices(self._h, C.c_void_p(out.data_ptr()), self._stream()),
+              "pgx_sde_actor_get_matrices", self.lib)
+        return out
+
+    @exploration_matrices.setter
+    def exploration_matrices(self, value: Any) -> None:
+        self._need_device()
+        t = self._dev(value, (self.n_envs, self.latent_dim, self.action_dim))
+        check(self.lib.pgx_sde_actor_set_matrices(self._h, C.c_void_p(t.data_ptr()), self._stream()),
+              "pgx_sde_actor_set_matrices", self.lib)
+        self._keep_m = t   # alive until the stream has consumed it
+
+    # --------------------------------------------------------------- forward
+    def _launch(self, obs: Dict[str, "torch.Tensor"], deterministic: bool) -> None:
+        d = self._debug
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        io = abi.PgxSdeActorIo(p(obs["observation"]), p(obs["achieved_goal"]), p(obs["desired_goal"]), p(self.actions),
+                               *([None] * 3 if d is None else [p(d[k]) for k in ("mean", "latent", "noise")]))
+        check(self.lib.pgx_sde_actor_forward(self._h, C.byref(io), 1 if deterministic else 0, self._stream()),
+              "pgx_sde_actor_forward", self.lib)
+
+    def _dev(self, x, shape) -> "torch.Tensor":
+        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+        if tuple(t.shape) != shape:
+            raise ValueError(f"expected shape {list(shape)}, got {list(t.shape)}")
+        return t.to(device=self.device, dtype=torch.float32).contiguous()   # a no-op for the env's own buffers
+
+    def __call__(self, obs: Dict[str, Any], deterministic: bool = False) -> "torch.Tensor":
+        """Actions [N, A] for the observation dict ``obs`` (what ``step_tensors`` / ``reset_tensors`` of an
+        env, a ``VecNormalize`` or a ``VecMonitor`` return; read in place): one launch.  ``deterministic``:
+        ``tanh(mean)``, no matrix is read.  Returns the actor's persistent action tensor (overwritten by
+        the next call)."""
+        self._need_device()
+        N = self.n_envs
+        o = {k: self._dev(obs[k], (N, self.obs_dim if k == "observation" else 3)) for k in OBS_KEYS}
+        self._launch(o, deterministic)
+        self._keep = [o]   # alive until the stream has consumed them
+        return self.actions
+
+    forward = __call__
+
+    def forward_host(self, obs: Dict[str, Any], matrices: Any):
+        """``(mean [n, A], latent [n, H], noise [n, A])`` numpy f32 from the library's host model of the
+        kernel's arithmetic, for any number of rows and their ``matrices`` [n, H, A].  A test oracle."""
+        o = {k: np.ascontiguousarray(obs[k].cpu().numpy() if torch.is_tensor(obs[k]) else obs[k], dtype=np.float32)
+             for k in OBS_KEYS}
+        n = o["observation"].shape[0]
+        H, A = max(self.latent_dim, 0), self.action_dim
+        m = np.ascontiguousarray(matrices.cpu().numpy() if torch.is_tensor(matrices) else matrices, dtype=np.float32)
+        if m.shape != (n, H, A):
+            raise ValueError(f"expected matrices of shape {[n, H, A]}, got {list(m.shape)}")
+        ws = [np.ascontiguousarray(t.cpu().numpy()) for t in self._w]
+        bs = [np.ascontiguousarray(t.cpu().numpy()) for t in self._b]
+        ls = np.ascontiguousarray(self._log_std.cpu().numpy())
+        w = self._weights_struct([x.ctypes.data for x in ws], [x.ctypes.data for x in bs], ls.ctypes.data)
+        mean, latent, noise = np.zeros((n, A), np.float32), np.zeros((n, H), np.float32), np.zeros((n, A), np.float32)
+        check(self.lib.pgx_sde_actor_forward_host(C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
+                                                  abi.ptr(o["achieved_goal"]), abi.ptr(o["desired_goal"]), abi.ptr(m), n,
+                                                  abi.ptr(mean), abi.ptr(latent), abi.ptr(noise)),
+              "pgx_sde_actor_forward_host", self.lib)
+        return mean, latent, noise
+
+    # --------------------------------------------------------------- rollouts
+    def _venv_obs(self, venv) -> Dict[str, "torch.Tensor"]:
+        from .rollout import step_buffers
+
+        self._need_device()
+        obs = step_buffers(venv)[0]
+        N = self.n_envs
+        for key in OBS_KEYS:
+            t = obs[key]
+            if tuple(t.shape) != (N, self.obs_dim if key == "observation" else 3) or t.dtype != torch.float32 \
+                    or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"venv's {key} buffer does not fit this actor")
+        return obs
+
+    def _enqueue_rollout(self, venv, obs, k: int, deterministic: bool, after_step, sde_sample_freq: int, what: str) -> None:
+        for j in range(int(k)):
+            if j == 0 or (sde_sample_freq > 0 and j % sde_sample_freq == 0):
+                self.reset_noise()
+            self._launch(obs, deterministic)
+            venv._enqueue_step(self.actions, what)
+            if after_step is not None:
+                after_step()
+
+    def capture_rollout(self, venv, k: int, deterministic: bool = False, after_step: Optional[Callable[[], None]] = None,
+                        sde_sample_freq: int = -1):
+        """Capture ``k`` closed-loop steps into one HIP graph (``torch.cuda.CUDAGraph``): one
+        ``reset_noise`` in front of step 0 and another before every step ``j > 0`` with ``sde_sample_freq
+        > 0 and j % sde_sample_freq == 0``; per step the forward on ``venv``'s persistent observation
+        buffers, ``venv._enqueue_step(self.actions)``, ``after_step()``.  With ``k = train_freq`` a replay
+        is one SB3 off-policy ``collect_rollouts``.  (SB3 resamples twice before step 0 when
+        ``sde_sample_freq > 0`` and throws the first draw away; here it is once.)  ``venv``: the env, a
+        ``VecNormalize`` or a ``VecMonitor``.  ``after_step``: e.g. ``buf.after_step(venv, actor.actions)``
+        of the HER ring.  Capture runs nothing; every replay draws new matrices (the generation word is
+        on the device) and uses the weights loaded last."""
+        obs = self._venv_obs(venv)
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._enqueue_rollout(venv, obs, k, deterministic, after_step, int(sde_sample_freq), "pgx_step (capture)")
+        g._pgx_keep = (self, obs)   # the graph reads these buffers at replay
+        return g
+
+    def collect(self, venv, k: int, deterministic: bool = False, after_step: Optional[Callable[[], None]] = None,
+                sde_sample_freq: int = -1) -> None:
+        """The launches of one ``capture_rollout`` replay, enqueued on the current stream without a graph."""
+        obs = self._venv_obs(venv)
+        self._enqueue_rollout(venv, obs, k, deterministic, after_step, int(sde_sample_freq), "pgx_step (collect)")
