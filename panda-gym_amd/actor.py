@@ -22,17 +22,10 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import abi
-from ._native import PgxError, check, load
-
-try:
-    import torch
-except ImportError:  # pragma: no cover
-    torch = None
-
-OBS_KEYS = ("observation", "achieved_goal", "desired_goal")
+from ._policy import OBS_KEYS, Policy, torch  # noqa: F401  (OBS_KEYS: importable from here as before)
 
 
-class Actor:
+class Actor(Policy):
     """SB3's SAC / TQC (``kind="gaussian"``) or TD3 / DDPG (``kind="deterministic"``) actor on the device.
 
     ``env``: a ``PandaVecEnv`` or a wrapper of one (``n_envs``, the dims and the device are read from
@@ -46,22 +39,10 @@ class Actor:
                  net_arch: Sequence[int] = (256, 256), kind: str = "gaussian", clip_mean: float = 0.0,
                  action_noise: Optional[Tuple[float, float]] = None, seed: int = 0, device: Any = None,
                  n_envs: Optional[int] = None):
-        if torch is None:
-            raise PgxError("Actor needs torch for its buffers")
+        self._need_torch()
         if kind not in abi.ACTOR_KINDS:
             raise ValueError(f"kind must be one of {list(abi.ACTOR_KINDS)}, got {kind!r}")
-        if env is not None:
-            n_envs = env.num_envs
-            obs_dim = env.obs_dim if obs_dim is None else obs_dim
-            action_dim = env.action_dim if action_dim is None else action_dim
-            device = env.device if device is None else device
-        if obs_dim is None or action_dim is None or n_envs is None:
-            raise ValueError("pass env, or obs_dim, action_dim and n_envs")
-        if int(n_envs) <= 0:
-            raise ValueError("n_envs must be > 0")
-        self.lib = load()
-        self.device = torch.device("cuda:0" if device is None else device)
-        self.n_envs, self.obs_dim, self.action_dim = int(n_envs), int(obs_dim), int(action_dim)
+        self._resolve(env, obs_dim, action_dim, n_envs, device)
         self.net_arch = tuple(int(w) for w in net_arch)
         self.kind, self.clip_mean, self.seed = kind, float(clip_mean), int(seed)
         self.action_noise = None if action_noise is None else (float(action_noise[0]), float(action_noise[1]))
@@ -76,7 +57,6 @@ class Actor:
         cfg.noise_mu, cfg.noise_sigma = self.action_noise or (0.0, 0.0)
         cfg.seed = self.seed & 0xFFFFFFFFFFFFFFFF
         self._cfg = cfg
-        self._h = None
         # the parameters as given (torch layout), on the actor's device: what set_weights reads
         dims = [self.obs_dim + 6] + list(self.net_arch)
         shapes = [(dims[i + 1], dims[i]) for i in range(len(self.net_arch))]
@@ -85,20 +65,12 @@ class Actor:
         self._w = [torch.zeros(s, dtype=torch.float32, device=self.device) for s in shapes]
         self._b = [torch.zeros(s[0], dtype=torch.float32, device=self.device) for s in shapes]
         self.actions = torch.zeros((self.n_envs, self.action_dim), dtype=torch.float32, device=self.device)
-        self._debug: Optional[Dict[str, "torch.Tensor"]] = None
-        self._keep: List[Any] = []
-        if self.device.type == "cuda":
-            h = C.c_void_p()
-            torch.cuda.set_device(self.device)
-            check(self.lib.pgx_actor_create(C.byref(cfg), self.device.index or 0, C.byref(h)), "pgx_actor_create",
-                  self.lib)
-            self._h = h
-            self._push()
-        else:   # the library's argument checks either way: the host model on no rows
-            self.forward_host({"observation": np.zeros((0, self.obs_dim), np.float32),
-                               "achieved_goal": np.zeros((0, 3), np.float32), "desired_goal": np.zeros((0, 3), np.float32)})
+        self._open()
 
     # ------------------------------------------------------------ plumbing
+    _PREFIX = "pgx_actor"
+    _SD_PREFIX = "actor."
+
     @staticmethod
     def _key_names(kind: str, n_layers: int) -> List[str]:
         """SB3's module names per parameter slot: the hidden layers, mu, log_std."""
@@ -106,13 +78,6 @@ class Actor:
             return [f"latent_pi.{2 * i}" for i in range(n_layers)] + ["mu", "log_std"]
         # td3/policies.py Actor: mu = Sequential(Linear, ReLU, ..., Linear, Tanh)
         return [f"mu.{2 * i}" for i in range(n_layers + 1)]
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _need_device(self):
-        if self._h is None:
-            raise PgxError("this Actor has no device handle (device='cpu' or closed): no CPU fallback")
 
     def _weights_struct(self, ws, bs) -> abi.PgxActorWeights:
         w = abi.PgxActorWeights()
@@ -122,49 +87,17 @@ class Actor:
 
     def _push(self) -> None:
         w = self._weights_struct([t.data_ptr() for t in self._w], [t.data_ptr() for t in self._b])
-        check(self.lib.pgx_actor_set_weights(self._h, C.byref(w), self._stream()), "pgx_actor_set_weights", self.lib)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            torch.cuda.synchronize(self.device)
-            self.lib.pgx_actor_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._lib_call("set_weights", self._h, C.byref(w), self._stream())
 
     # ----------------------------------------------------------- parameters
-    def state_dict(self) -> Dict[str, "torch.Tensor"]:
-        """The parameters under SB3's actor key names (copies, on the actor's device)."""
-        out = {}
-        for name, w, b in zip(self._names, self._w, self._b):
-            out[f"{name}.weight"], out[f"{name}.bias"] = w.clone(), b.clone()
-        return out
+    _slots = Policy._pairs
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
         """Load SB3 actor parameters: ``latent_pi.{0,2,4}`` / ``mu`` / ``log_std`` (SAC, TQC) or
         ``mu.{0,2,4,...}`` (TD3, DDPG), ``.weight`` [out, in] and ``.bias`` [out]; a policy's state
         dict works too (its ``actor.`` keys are read, the rest ignored).  The packed weights in the
         handle are replaced on the current stream: a captured graph uses them at its next replay."""
-        if any(k.startswith("actor.") for k in sd):
-            sd = {k[len("actor."):]: v for k, v in sd.items() if k.startswith("actor.")}
-        new_w, new_b = [], []
-        for name, w, b in zip(self._names, self._w, self._b):
-            for key, cur, dst in ((f"{name}.weight", w, new_w), (f"{name}.bias", b, new_b)):
-                if key not in sd:
-                    raise KeyError(f"load_state_dict: missing key {key!r}")
-                v = sd[key]
-                t = v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
-                if tuple(t.shape) != tuple(cur.shape):
-                    raise ValueError(f"load_state_dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(cur.shape)}")
-                dst.append(t.to(device=self.device, dtype=torch.float32).contiguous())
-        for cur, new in zip(self._w + self._b, new_w + new_b):
-            cur.copy_(new)   # in place: the handle's copies read these same buffers
-        if self._h is not None:
-            self._push()
+        self._load_slots(sd)   # validates every key, then copies
 
     # --------------------------------------------------------------- forward
     def enable_debug(self) -> Dict[str, "torch.Tensor"]:
@@ -183,13 +116,7 @@ class Actor:
         io = abi.PgxActorIo(p(obs["observation"]), p(obs["achieved_goal"]), p(obs["desired_goal"]), p(self.actions),
                             p(eps), *([None] * 4 if d is None else [p(d[k]) for k in ("mean", "log_std", "eps", "philox")]))
         det = 1 if (deterministic or (self.kind == "deterministic" and self.action_noise is None)) else 0
-        check(self.lib.pgx_actor_forward(self._h, C.byref(io), det, self._stream()), "pgx_actor_forward", self.lib)
-
-    def _dev(self, x, shape) -> "torch.Tensor":
-        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-        if tuple(t.shape) != shape:
-            raise ValueError(f"expected shape {list(shape)}, got {list(t.shape)}")
-        return t.to(device=self.device, dtype=torch.float32).contiguous()   # a no-op for the env's own buffers
+        self._lib_call("forward", self._h, C.byref(io), det, self._stream())
 
     def __call__(self, obs: Dict[str, Any], deterministic: bool = False, eps: Any = None) -> "torch.Tensor":
         """Actions [N, A] for the observation dict ``obs`` (what ``step_tensors`` / ``reset_tensors`` of
@@ -197,9 +124,8 @@ class Actor:
         [N, A]: the Gaussian noise to use instead of the device stream.  Returns the actor's
         persistent action tensor (overwritten by the next call)."""
         self._need_device()
-        N = self.n_envs
-        o = {k: self._dev(obs[k], (N, self.obs_dim if k == "observation" else 3)) for k in OBS_KEYS}
-        e = None if eps is None else self._dev(eps, (N, self.action_dim))
+        o = self._obs(obs)
+        e = None if eps is None else self._dev(eps, (self.n_envs, self.action_dim))
         self._launch(o, deterministic, e)
         self._keep = [o, e]   # alive until the stream has consumed them
         return self.actions
@@ -209,33 +135,16 @@ class Actor:
     def forward_host(self, obs: Dict[str, Any]):
         """``(mean, log_std)`` [n, A] numpy f32 from the library's host model of the kernel's arithmetic
         (``log_std`` None for the deterministic kind), for any number of rows.  A test oracle."""
-        o = {k: np.ascontiguousarray(obs[k].cpu().numpy() if torch.is_tensor(obs[k]) else obs[k], dtype=np.float32)
-             for k in OBS_KEYS}
-        n = o["observation"].shape[0]
-        ws = [np.ascontiguousarray(t.cpu().numpy()) for t in self._w]
-        bs = [np.ascontiguousarray(t.cpu().numpy()) for t in self._b]
+        (o, n), (ws, bs) = self._host_obs(obs), self._host_params()
         w = self._weights_struct([x.ctypes.data for x in ws], [x.ctypes.data for x in bs])
         mean = np.zeros((n, self.action_dim), np.float32)
         log_std = np.zeros((n, self.action_dim), np.float32) if self.kind == "gaussian" else None
-        check(self.lib.pgx_actor_forward_host(C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
-                                              abi.ptr(o["achieved_goal"]), abi.ptr(o["desired_goal"]), n, abi.ptr(mean),
-                                              abi.ptr(log_std)), "pgx_actor_forward_host", self.lib)
+        self._lib_call("forward_host", C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
+                       abi.ptr(o["achieved_goal"]), abi.ptr(o["desired_goal"]), n, abi.ptr(mean), abi.ptr(log_std))
         return mean, log_std
 
-    @property
-    def noise_step(self) -> int:
-        """The device word that counts the forwards that drew noise from the Philox stream (this
-        synchronises).  Setting it back reproduces the draws."""
-        self._need_device()
-        v = C.c_uint64(0)
-        check(self.lib.pgx_actor_state(self._h, C.byref(v), self._stream()), "pgx_actor_state", self.lib)
-        return int(v.value)
-
-    @noise_step.setter
-    def noise_step(self, value: int) -> None:
-        self._need_device()
-        check(self.lib.pgx_actor_set_state(self._h, C.c_uint64(int(value) & 0xFFFFFFFFFFFFFFFF), self._stream()),
-              "pgx_actor_set_state", self.lib)
+    noise_step = property(Policy._get_word, Policy._set_word, doc="""The device word that counts the forwards that
+        drew noise from the Philox stream (this synchronises).  Setting it back reproduces the draws.""")
 
     # --------------------------------------------------------------- capture
     def capture_rollout(self, venv, k: int, deterministic: bool = False, after_step: Optional[Callable[[], None]] = None):
@@ -249,12 +158,7 @@ class Actor:
 
         self._need_device()
         obs = step_buffers(venv)[0]
-        N = self.n_envs
-        for key in OBS_KEYS:
-            t = obs[key]
-            if tuple(t.shape) != (N, self.obs_dim if key == "observation" else 3) or t.dtype != torch.float32 \
-                    or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"venv's {key} buffer does not fit this actor")
+        self._check_venv_obs(obs)
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):

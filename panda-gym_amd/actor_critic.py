@@ -23,14 +23,9 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import abi
-from ._native import PgxError, check, load
+from ._native import PgxError
+from ._policy import Policy, torch
 
-try:
-    import torch
-except ImportError:  # pragma: no cover
-    torch = None
-
-OBS_KEYS = ("observation", "achieved_goal", "desired_goal")
 DEFAULT_NET_ARCH = {"pi": (256, 256), "vf": (256, 256)}   # the reference's PPO setting
 
 
@@ -40,7 +35,7 @@ def _is_relu(fn: Any) -> bool:
     return torch is not None and (fn is torch.nn.ReLU or isinstance(fn, torch.nn.ReLU))
 
 
-class ActorCritic:
+class ActorCritic(Policy):
     """SB3's ``ActorCriticPolicy`` (``MultiInputPolicy``, PPO / A2C) forward on the device.
 
     ``env``: a ``PandaVecEnv`` or a wrapper of one (``n_envs``, the dims and the device are read from
@@ -55,20 +50,11 @@ class ActorCritic:
                  n_envs: Optional[int] = None, net_arch: Union[None, Dict[str, Sequence[int]], Sequence[int]] = None,
                  log_std_init: float = 0.0, activation_fn: Any = "relu", use_sde: bool = False, seed: int = 0,
                  device: Any = None):
-        if torch is None:
-            raise PgxError("ActorCritic needs torch for its buffers")
+        self._need_torch()
         if not _is_relu(activation_fn):
             raise ValueError(f"activation_fn {activation_fn!r}: only ReLU is built; SB3's default Tanh is not (a device "
                              "tanhf in the trunk cannot meet the bit-exact host model)")
-        if env is not None:
-            n_envs = env.num_envs
-            obs_dim = env.obs_dim if obs_dim is None else obs_dim
-            action_dim = env.action_dim if action_dim is None else action_dim
-            device = env.device if device is None else device
-        if obs_dim is None or action_dim is None or n_envs is None:
-            raise ValueError("pass env, or obs_dim, action_dim and n_envs")
-        if int(n_envs) <= 0:
-            raise ValueError("n_envs must be > 0")
+        self._resolve(env, obs_dim, action_dim, n_envs, device)
         arch = DEFAULT_NET_ARCH if net_arch is None else net_arch
         if isinstance(arch, dict):
             if set(arch) != {"pi", "vf"}:
@@ -76,9 +62,6 @@ class ActorCritic:
             pi, vf = arch["pi"], arch["vf"]
         else:
             pi = vf = arch
-        self.lib = load()
-        self.device = torch.device("cuda:0" if device is None else device)
-        self.n_envs, self.obs_dim, self.action_dim = int(n_envs), int(obs_dim), int(action_dim)
         self.pi_arch, self.vf_arch = tuple(int(w) for w in pi), tuple(int(w) for w in vf)
         self.net_arch = {"pi": self.pi_arch, "vf": self.vf_arch}
         self.log_std_init, self.use_sde, self.seed = float(log_std_init), bool(use_sde), int(seed)
@@ -91,7 +74,6 @@ class ActorCritic:
             cfg.vf_hidden[i] = w
         cfg.seed = self.seed & 0xFFFFFFFFFFFFFFFF
         self._cfg = cfg
-        self._h = None
         # the parameters as given (torch layout), on this device: what set_weights reads
         N, A, in_dim = self.n_envs, self.action_dim, self.obs_dim + 6
         self._names: List[str] = []
@@ -113,25 +95,11 @@ class ActorCritic:
         self.actions, self.clipped_actions = z(N, A), z(N, A)
         self.values, self.log_probs = z(N), z(N)
         self.terminal_values, self.last_values, self._pv = z(N), z(N), z(N)
-        self._debug: Optional[Dict[str, "torch.Tensor"]] = None
-        self._keep: List[Any] = []
-        if self.device.type == "cuda":
-            h = C.c_void_p()
-            torch.cuda.set_device(self.device)
-            check(self.lib.pgx_ac_create(C.byref(cfg), self.device.index or 0, C.byref(h)), "pgx_ac_create", self.lib)
-            self._h = h
-            self._push()
-        else:   # the library's argument checks either way: the host model on no rows
-            self.forward_host({"observation": np.zeros((0, self.obs_dim), np.float32),
-                               "achieved_goal": np.zeros((0, 3), np.float32), "desired_goal": np.zeros((0, 3), np.float32)})
+        self._open()
 
     # ------------------------------------------------------------ plumbing
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _need_device(self):
-        if self._h is None:
-            raise PgxError("this ActorCritic has no device handle (device='cpu' or closed): no CPU fallback")
+    _PREFIX = "pgx_ac"
+    _WHO = "ActorCritic"
 
     def _weights_struct(self, ws, bs, log_std) -> abi.PgxAcWeights:
         w = abi.PgxAcWeights()
@@ -149,27 +117,16 @@ class ActorCritic:
     def _push(self) -> None:
         w = self._weights_struct([t.data_ptr() for t in self._w], [t.data_ptr() for t in self._b],
                                  self._log_std_lib.data_ptr())
-        check(self.lib.pgx_ac_set_weights(self._h, C.byref(w), self._stream()), "pgx_ac_set_weights", self.lib)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            torch.cuda.synchronize(self.device)
-            self.lib.pgx_ac_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._lib_call("set_weights", self._h, C.byref(w), self._stream())
 
     # ----------------------------------------------------------- parameters
-    def state_dict(self) -> Dict[str, "torch.Tensor"]:
-        """The parameters under SB3's ``ActorCriticPolicy`` key names (copies, on this device)."""
-        out = {"log_std": self._log_std.clone()}
-        for name, w, b in zip(self._names, self._w, self._b):
-            out[f"{name}.weight"], out[f"{name}.bias"] = w.clone(), b.clone()
-        return out
+    def _slots(self):
+        """(key, tensor) of every parameter: ``log_std`` first, then SB3's ``ActorCriticPolicy`` names."""
+        return [("log_std", self._log_std)] + self._pairs()
+
+    def _shape_hint(self, key: str) -> str:
+        return " (use_sde=True expects SB3's gSDE log_std [last pi width, action_dim])" \
+            if key == "log_std" and self.use_sde else ""
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
         """Load an SB3 ``ActorCriticPolicy`` state dict: ``mlp_extractor.policy_net.{0,2,4}``,
@@ -178,24 +135,7 @@ class ActorCritic:
         (``features_extractor.*``, ...) are ignored.  A failed load changes nothing.  The packed
         weights in the handle are replaced on the current stream: a captured graph uses them at its
         next replay."""
-        cur = [("log_std", self._log_std)]
-        for name, w, b in zip(self._names, self._w, self._b):
-            cur += [(f"{name}.weight", w), (f"{name}.bias", b)]
-        new = []
-        for key, dst in cur:
-            if key not in sd:
-                raise KeyError(f"load_state_dict: missing key {key!r}")
-            v = sd[key]
-            t = v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
-            if tuple(t.shape) != tuple(dst.shape):
-                hint = " (use_sde=True expects SB3's gSDE log_std [last pi width, action_dim])" \
-                    if key == "log_std" and self.use_sde else ""
-                raise ValueError(f"load_state_dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(dst.shape)}{hint}")
-            new.append(t.to(device=self.device, dtype=torch.float32).contiguous())
-        for (_, dst), t in zip(cur, new):
-            dst.copy_(t)   # in place: the handle's copies read these same buffers
-        if self._h is not None:
-            self._push()
+        self._load_slots(sd)   # validates every key, then copies
 
     # --------------------------------------------------------------- forward
     def enable_debug(self) -> Dict[str, "torch.Tensor"]:
@@ -215,23 +155,12 @@ class ActorCritic:
         io = abi.PgxAcIo(p(obs["observation"]), p(obs["achieved_goal"]), p(obs["desired_goal"]), p(self.actions),
                          p(self.clipped_actions), p(self.values), p(self.log_probs), p(eps),
                          *([None] * 3 if d is None else [p(d[k]) for k in ("mean", "eps", "philox")]))
-        check(self.lib.pgx_ac_forward(self._h, C.byref(io), 1 if deterministic else 0, self._stream()), "pgx_ac_forward",
-              self.lib)
+        self._lib_call("forward", self._h, C.byref(io), 1 if deterministic else 0, self._stream())
 
     def _launch_values(self, obs: Dict[str, "torch.Tensor"], need: Optional["torch.Tensor"], out: "torch.Tensor") -> None:
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        check(self.lib.pgx_ac_values(self._h, p(obs["observation"]), p(obs["achieved_goal"]), p(obs["desired_goal"]),
-                                     p(need), p(out), self._stream()), "pgx_ac_values", self.lib)
-
-    def _dev(self, x, shape) -> "torch.Tensor":
-        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-        if tuple(t.shape) != shape:
-            raise ValueError(f"expected shape {list(shape)}, got {list(t.shape)}")
-        return t.to(device=self.device, dtype=torch.float32).contiguous()   # a no-op for the env's own buffers
-
-    def _obs(self, obs: Dict[str, Any]) -> Dict[str, "torch.Tensor"]:
-        N = self.n_envs
-        return {k: self._dev(obs[k], (N, self.obs_dim if k == "observation" else 3)) for k in OBS_KEYS}
+        self._lib_call("values", self._h, p(obs["observation"]), p(obs["achieved_goal"]), p(obs["desired_goal"]),
+                       p(need), p(out), self._stream())
 
     def __call__(self, obs: Dict[str, Any], deterministic: bool = False, eps: Any = None):
         """SB3's ``policy.forward``: ``(actions [N, A], values [N], log_probs [N])`` for the observation
@@ -278,34 +207,17 @@ class ActorCritic:
     def forward_host(self, obs: Dict[str, Any]):
         """``(mean [n, A], value [n])`` numpy f32 from the library's host model of the kernel's
         arithmetic, for any number of rows.  A test oracle."""
-        o = {k: np.ascontiguousarray(obs[k].cpu().numpy() if torch.is_tensor(obs[k]) else obs[k], dtype=np.float32)
-             for k in OBS_KEYS}
-        n = o["observation"].shape[0]
-        ws = [np.ascontiguousarray(t.cpu().numpy()) for t in self._w]
-        bs = [np.ascontiguousarray(t.cpu().numpy()) for t in self._b]
+        (o, n), (ws, bs) = self._host_obs(obs), self._host_params()
         ls = np.ascontiguousarray(self._log_std_lib.cpu().numpy())
         w = self._weights_struct([x.ctypes.data for x in ws], [x.ctypes.data for x in bs], ls.ctypes.data)
         mean = np.zeros((n, self.action_dim), np.float32)
         value = np.zeros((n,), np.float32)
-        check(self.lib.pgx_ac_forward_host(C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
-                                           abi.ptr(o["achieved_goal"]), abi.ptr(o["desired_goal"]), n, abi.ptr(mean),
-                                           abi.ptr(value)), "pgx_ac_forward_host", self.lib)
+        self._lib_call("forward_host", C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
+                       abi.ptr(o["achieved_goal"]), abi.ptr(o["desired_goal"]), n, abi.ptr(mean), abi.ptr(value))
         return mean, value
 
-    @property
-    def noise_step(self) -> int:
-        """The device word that counts the forwards that drew noise from the Philox stream (this
-        synchronises).  Setting it back reproduces the draws."""
-        self._need_device()
-        v = C.c_uint64(0)
-        check(self.lib.pgx_ac_state(self._h, C.byref(v), self._stream()), "pgx_ac_state", self.lib)
-        return int(v.value)
-
-    @noise_step.setter
-    def noise_step(self, value: int) -> None:
-        self._need_device()
-        check(self.lib.pgx_ac_set_state(self._h, C.c_uint64(int(value) & 0xFFFFFFFFFFFFFFFF), self._stream()),
-              "pgx_ac_set_state", self.lib)
+    noise_step = property(Policy._get_word, Policy._set_word, doc="""The device word that counts the forwards that
+        drew noise from the Philox stream (this synchronises).  Setting it back reproduces the draws.""")
 
     # -------------------------------------------------------------- rollouts
     def _rollout_buffers(self, venv, buf):
@@ -319,14 +231,9 @@ class ActorCritic:
             raise ValueError("the RolloutBuffer does not fit this ActorCritic")
         obs, reward, terminated, truncated = step_buffers(venv)
         tobs = terminal_observation(venv)
-        N = self.n_envs
-        for o in (obs, tobs):
-            for key in OBS_KEYS:
-                t = o[key]
-                if tuple(t.shape) != (N, self.obs_dim if key == "observation" else 3) or t.dtype != torch.float32 \
-                        or t.device != self.device or not t.is_contiguous():
-                    raise ValueError(f"venv's {key} buffer does not fit this ActorCritic")
-        if truncated.dtype != torch.uint8 or tuple(truncated.shape) != (N,) or not truncated.is_contiguous():
+        self._check_venv_obs(obs)
+        self._check_venv_obs(tobs)
+        if truncated.dtype != torch.uint8 or tuple(truncated.shape) != (self.n_envs,) or not truncated.is_contiguous():
             raise ValueError("venv's truncated flags must be a contiguous uint8 [N] tensor")
         return obs, reward, terminated, truncated, tobs
 

@@ -17,33 +17,24 @@
  * as one 16-byte load per lane per 16 k, fetched one block ahead of the MFMAs that use them.  The
  * tail is masked: envs past N are staged as zero rows and never stored, the K remainder of the
  * input is staged as +0 against zero weights.
- * The noise step word: thread 0 reads it into LDS ahead of the first barrier; the last workgroup
- * to take a ticket, behind every workgroup's read, adds one and clears the ticket.
+ * The staging, the Linear, the loop over the layers, the Gaussian draw and the noise step word's read
+ * and advance are pgx_mlp.h's, shared with the other policy units; the epilogue is this unit's.  The
+ * host-side plan, allocation and packing are pgx_policy.h's.
  */
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <cstdlib>
+#include "pgx_policy.h"   /* pgx_mlp.h, pgx_common.h, include/pgx.h */
 
-#include "../../include/pgx.h"
-#include "pgx_common.h"
-#include "pgx_mlp.h"   /* linear_layer, pack_kernel, WAVES, NACC, f32x4 */
-
-int pgx_set_error(int code, const char* msg);  /* pgx_api.cpp: sets pgx_last_error() */
 int pgx_actor_check_config(const pgx_actor_config* c, const char* what, bool with_envs);  /* pgx_actor_host.cpp */
 
 namespace {
 
 constexpr uint32_t TAG_ACTOR = 0x41435430u;
-constexpr int THREADS = 64 * WAVES;
-constexpr int MAX_LINEAR = PGX_ACTOR_MAX_LAYERS + 1;   /* the hidden layers and the head tile */
 constexpr int LOG_STD_ROW = 8;  /* the head tile: mu in rows 0..6, log_std in rows 8..14 */
 
 struct ActorArgs {
-    int32_t n, od, ad, n_linear, kind, S;   /* S: LDS row stride (floats) */
+    int32_t n, od, ad, kind, S;   /* S: LDS row stride (floats) */
     float clip, noise_mu, noise_sigma;
     uint32_t seed_lo, seed_hi;
-    int32_t nkb[MAX_LINEAR], ntiles[MAX_LINEAR];   /* 16-wide k blocks and output tiles per Linear */
-    int32_t woff[MAX_LINEAR], boff[MAX_LINEAR];    /* packed weights / padded bias, floats into params */
+    MlpPlan plan;                 /* the trunk and the head tile */
     const float* params;
     unsigned long long* step;
     uint32_t* ticket;
@@ -58,30 +49,11 @@ __global__ __launch_bounds__(THREADS) void actor_forward_kernel(ActorArgs a, pgx
     const int S = a.S, N = a.n, od = a.od, A = a.ad;
     const int env0 = blockIdx.x * ROWS;
     const bool draw = deterministic == 0 && io.eps == nullptr;
-    if (tid == 0) sh_step = draw ? *a.step : 0ull;
-    /* features: achieved_goal | desired_goal | observation, +0 past in_dim and past env N */
-    const int K0 = a.nkb[0] * 16, in_dim = od + 6;
-    for (int idx = tid; idx < ROWS * K0; idx += THREADS) {
-        const int r = idx / K0, k = idx - r * K0;
-        const int e = env0 + r;
-        float v = 0.0f;
-        if (e < N && k < in_dim) {
-            if (k < 3) v = io.achieved_goal[(size_t)e * 3 + k];
-            else if (k < 6) v = io.desired_goal[(size_t)e * 3 + (k - 3)];
-            else v = io.obs[(size_t)e * od + (k - 6)];
-        }
-        lds[r * S + k] = v;
-    }
+    load_word(&sh_step, a.step, draw, tid);
+    stage_features<MT>(lds, io.obs, io.achieved_goal, io.desired_goal, env0, N, od, a.plan.nkb[0] * 16, S, tid);
     __syncthreads();
-    int in_off = 0, out_off = ROWS * S;
-    for (int l = 0; l < a.n_linear; l++) {
-        linear_layer<MT>(lds, in_off, out_off, a.params + a.woff[l], a.params + a.boff[l], a.nkb[l], a.ntiles[l], S,
-                         l + 1 < a.n_linear, lane, wave);
-        __syncthreads();
-        const int t = in_off;
-        in_off = out_off;
-        out_off = t;
-    }
+    /* the features lie in region 0; it and region ROWS * S take turns */
+    const int in_off = run_linears<MT>(lds, a.params, a.plan, a.plan.n_linear, false, 0, S, ROWS * S, 0, S, lane, wave);
     /* epilogue: one thread per (env, dimension); the head tile lies at lds[in_off] */
     const int r = tid >> 3, d = tid & 7;
     const int e = env0 + r;
@@ -91,22 +63,8 @@ __global__ __launch_bounds__(THREADS) void actor_forward_kernel(ActorArgs a, pgx
         if (a.clip > 0.0f) mean = mean < -a.clip ? -a.clip : (mean > a.clip ? a.clip : mean);
         float eps = 0.0f;
         if (deterministic == 0) {
-            if (io.eps) {
-                eps = io.eps[(size_t)e * A + d];
-            } else {
-                const unsigned long long step = sh_step;
-                uint32_t rr[4];
-                philox((uint32_t)step, (uint32_t)(step >> 32), (uint32_t)e, TAG_ACTOR ^ (uint32_t)(d >> 1), a.seed_lo,
-                       a.seed_hi, rr);
-                const float u1 = (float)((rr[0] >> 8) + 1u) * 5.9604644775390625e-8f;
-                const float u2 = (float)(rr[1] >> 8) * 5.9604644775390625e-8f;
-                const float rad = sqrtf(-2.0f * logf(u1)), ang = 6.2831855f * u2;
-                eps = (d & 1) ? rad * sinf(ang) : rad * cosf(ang);
-                if (io.philox_out && (d & 1) == 0) {
-                    uint32_t* o = io.philox_out + ((size_t)e * 4 + (d >> 1)) * 4;
-                    o[0] = rr[0]; o[1] = rr[1]; o[2] = rr[2]; o[3] = rr[3];
-                }
-            }
+            if (io.eps) eps = io.eps[(size_t)e * A + d];
+            else eps = gaussian_draw(sh_step, e, d, TAG_ACTOR, a.seed_lo, a.seed_hi, io.philox_out);
         }
         float act;
         if (a.kind == PGX_ACTOR_GAUSSIAN) {
@@ -123,15 +81,7 @@ __global__ __launch_bounds__(THREADS) void actor_forward_kernel(ActorArgs a, pgx
         if (io.mean_out) io.mean_out[(size_t)e * A + d] = mean;
         if (io.eps_out) io.eps_out[(size_t)e * A + d] = eps;
     }
-    /* every workgroup has read the step word (ahead of its first barrier): the last one to arrive
-     * moves it on */
-    if (draw && tid == 0) {
-        __threadfence();
-        if (atomicAdd(a.ticket, 1u) == gridDim.x - 1) {
-            *a.ticket = 0u;
-            *a.step = sh_step + 1ull;
-        }
-    }
+    advance_word(a.step, a.ticket, &sh_step, gridDim.x, draw, tid);
 }
 
 }  // namespace
@@ -140,36 +90,17 @@ struct pgx_actor {
     int device;
     pgx_actor_config cfg;
     ActorArgs a;
-    void* blob;
-    float* params;              /* packed weights and padded biases */
+    float* params;              /* packed weights and padded biases; the head of the one allocation */
     float* plain;               /* the parameters as given, torch layout */
-    size_t plain_w[5], plain_b[5];
+    size_t plain_w[5], plain_b[5];   /* per slot: the hidden layers, mu, log_std */
     int mt;                     /* env tiles of 16 per workgroup */
     size_t lds_bytes;
 };
 
-namespace {
-
-constexpr size_t LDS_LIMIT = 160 * 1024;
-
-/* (out, in) of parameter slot i: the hidden layers, mu, log_std */
-void slot_dims(const pgx_actor_config& c, int i, int* out, int* in) {
-    const int nl = c.n_layers;
-    if (i < nl) {
-        *out = c.hidden[i];
-        *in = i == 0 ? c.obs_dim + 6 : c.hidden[i - 1];
-    } else {
-        *out = c.action_dim;
-        *in = c.hidden[nl - 1];
-    }
-}
-
-}  // namespace
-
 extern "C" {
 
 int pgx_actor_create(const pgx_actor_config* cfg, int device, pgx_actor_handle* out) {
-    const int rc = pgx_actor_check_config(cfg, "pgx_actor_create", true);
+    int rc = pgx_actor_check_config(cfg, "pgx_actor_create", true);
     if (rc != PGX_OK) return rc;
     if (!out) return pgx_set_error(PGX_E_INVALID, "pgx_actor_create: null handle pointer");
     *out = nullptr;
@@ -177,74 +108,44 @@ int pgx_actor_create(const pgx_actor_config* cfg, int device, pgx_actor_handle* 
     h->device = device;
     h->cfg = *cfg;
     ActorArgs& a = h->a;
-    const int nl = cfg->n_layers, heads = cfg->kind == PGX_ACTOR_GAUSSIAN ? 2 : 1;
+    const int nl = cfg->n_layers;
     a.n = cfg->n_envs;
     a.od = cfg->obs_dim;
     a.ad = cfg->action_dim;
-    a.n_linear = nl + 1;
     a.kind = cfg->kind;
     a.clip = (float)cfg->clip_mean;
     a.noise_mu = (float)cfg->noise_mu;
     a.noise_sigma = (float)cfg->noise_sigma;
     a.seed_lo = (uint32_t)cfg->seed;
     a.seed_hi = (uint32_t)(cfg->seed >> 32);
-    size_t off = 0;
-    int widest = 16;
-    for (int l = 0; l <= nl; l++) {
-        int o, in;
-        slot_dims(*cfg, l, &o, &in);
-        a.nkb[l] = (in + 15) / 16;
-        a.ntiles[l] = l < nl ? (o + 15) / 16 : 1;
-        a.woff[l] = (int32_t)off;
-        off += (size_t)a.nkb[l] * a.ntiles[l] * 256;
-        a.boff[l] = (int32_t)off;
-        off += (size_t)a.ntiles[l] * 16;
-        if (a.nkb[l] * 16 > widest) widest = a.nkb[l] * 16;
+    size_t n_params = 0, n_plain = 0;
+    a.S = 4 + plan_stack(&a.plan, cfg->obs_dim + 6, cfg->hidden, nl, cfg->action_dim, 0, &n_params, h->plain_w,
+                         h->plain_b, &n_plain);
+    if (cfg->kind == PGX_ACTOR_GAUSSIAN) {   /* log_std: a plain slot more, packed into mu's tile */
+        h->plain_w[nl + 1] = n_plain;
+        n_plain += (size_t)cfg->action_dim * cfg->hidden[nl - 1];
+        h->plain_b[nl + 1] = n_plain;
+        n_plain += (size_t)cfg->action_dim;
     }
-    a.S = widest + 4;
-    const size_t n_params = off;
-    size_t n_plain = 0;
-    for (int i = 0; i < nl + heads; i++) {
-        int o, in;
-        slot_dims(*cfg, i, &o, &in);
-        h->plain_w[i] = n_plain;
-        n_plain += (size_t)o * in;
-        h->plain_b[i] = n_plain;
-        n_plain += (size_t)o;
-    }
-    /* 32 envs per workgroup from 4096 envs on: each workgroup streams every weight once, and at
-     * 4096 x [256, 256] the halved L2 traffic outweighs the halved workgroup count */
-    h->mt = cfg->n_envs >= 4096 ? 2 : 1;
-    if (const char* t = std::getenv("PGX_ACTOR_TILE")) h->mt = std::atoi(t) == 32 ? 2 : 1;
-    if (2 * (size_t)h->mt * 16 * a.S * 4 > LDS_LIMIT) h->mt = 1;
-    h->lds_bytes = 2 * (size_t)h->mt * 16 * a.S * 4;
-    if (h->lds_bytes > LDS_LIMIT) {
+    auto lds_need = [&a](int mt) { return 2 * (size_t)mt * 16 * a.S * 4; };
+    h->mt = choose_tile(cfg->n_envs, "PGX_ACTOR_TILE", lds_need);
+    if (h->mt == 0) {
         delete h;
         return pgx_set_error(PGX_E_UNSUPPORTED, "pgx_actor_create: obs_dim too wide for the activations in LDS");
     }
-    if (hipSetDevice(device) != hipSuccess) {
-        delete h;
-        return pgx_set_error(PGX_E_HIP, "pgx_actor_create: hipSetDevice");
-    }
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_plain = al(n_params * 4), o_words = al(o_plain + n_plain * 4), total = o_words + 256;
-    if (hipMalloc(&h->blob, total) != hipSuccess) {
-        delete h;
-        return pgx_set_error(PGX_E_NOMEM, "pgx_actor_create: hipMalloc failed");
-    }
+    h->lds_bytes = lds_need(h->mt);
+    const size_t bytes[3] = {n_params * 4, n_plain * 4, 256};
+    void* ptr[3];
     const void* fn = h->mt == 2 ? (const void*)actor_forward_kernel<2> : (const void*)actor_forward_kernel<1>;
-    if (hipMemset(h->blob, 0, total) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes) != hipSuccess) {
-        (void)hipFree(h->blob);
+    rc = create_blob("pgx_actor_create", device, bytes, 3, ptr, {fn}, h->lds_bytes);
+    if (rc != PGX_OK) {
         delete h;
-        return pgx_set_error(PGX_E_HIP, "pgx_actor_create: device setup failed");
+        return rc;
     }
-    char* b = (char*)h->blob;
-    h->params = (float*)b;
-    h->plain = (float*)(b + o_plain);
-    a.params = h->params;
-    a.step = (unsigned long long*)(b + o_words);
-    a.ticket = (uint32_t*)(b + o_words + 8);
+    a.params = h->params = (float*)ptr[0];
+    h->plain = (float*)ptr[1];
+    a.step = (unsigned long long*)ptr[2];
+    a.ticket = (uint32_t*)((char*)ptr[2] + 8);
     *out = h;
     return PGX_OK;
 }
@@ -252,7 +153,7 @@ int pgx_actor_create(const pgx_actor_config* cfg, int device, pgx_actor_handle* 
 void pgx_actor_destroy(pgx_actor_handle h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    (void)hipFree(h->blob);
+    (void)hipFree(h->params);
     delete h;
 }
 
@@ -263,18 +164,14 @@ int pgx_actor_set_weights(pgx_actor_handle h, const pgx_actor_weights* w, void* 
         if (!w->weight[i] || !w->bias[i])
             return pgx_set_error(PGX_E_INVALID, "pgx_actor_set_weights: null weight or bias pointer");
     hipStream_t st = (hipStream_t)stream;
+    const MlpPlan& p = h->a.plan;
     for (int i = 0; i < nl + heads; i++) {
+        const int l = i < nl ? i : nl;   /* mu and log_std share the head tile */
         int o, in;
-        slot_dims(h->cfg, i, &o, &in);
-        float* pw = h->plain + h->plain_w[i];
-        float* pb = h->plain + h->plain_b[i];
-        if (hipMemcpyAsync(pw, w->weight[i], (size_t)o * in * 4, hipMemcpyDefault, st) != hipSuccess ||
-            hipMemcpyAsync(pb, w->bias[i], (size_t)o * 4, hipMemcpyDefault, st) != hipSuccess)
+        linear_dims(h->cfg.obs_dim + 6, h->cfg.hidden, nl, h->cfg.action_dim, l, &o, &in);
+        if (!pack_linear(w->weight[i], w->bias[i], h->plain + h->plain_w[i], h->plain + h->plain_b[i], o, in,
+                         h->params + p.woff[l], h->params + p.boff[l], p.ntiles[l], i > nl ? LOG_STD_ROW : 0, st))
             return pgx_set_error(PGX_E_HIP, "pgx_actor_set_weights: copy failed");
-        const int l = i < nl ? i : nl;
-        const int n = o * in + o;
-        hipLaunchKernelGGL(pack_kernel, dim3((n + 255) / 256), dim3(256), 0, st, pw, pb, h->params + h->a.woff[l],
-                           h->params + h->a.boff[l], o, in, h->a.ntiles[l], i > nl ? LOG_STD_ROW : 0);
     }
     return hipGetLastError() == hipSuccess ? PGX_OK : pgx_set_error(PGX_E_HIP, "pgx_actor_set_weights: launch failed");
 }
@@ -283,34 +180,19 @@ int pgx_actor_forward(pgx_actor_handle h, const pgx_actor_io* io, int32_t determ
     if (!h || !io) return pgx_set_error(PGX_E_INVALID, "pgx_actor_forward: null handle or io");
     if (!io->obs || !io->achieved_goal || !io->desired_goal || !io->action)
         return pgx_set_error(PGX_E_INVALID, "pgx_actor_forward: null observation or action pointer");
-    const int rows = h->mt * 16;
-    const dim3 grid((h->a.n + rows - 1) / rows);
-    if (h->mt == 2)
-        hipLaunchKernelGGL(actor_forward_kernel<2>, grid, dim3(THREADS), h->lds_bytes, (hipStream_t)stream, h->a, *io,
-                           deterministic);
-    else
-        hipLaunchKernelGGL(actor_forward_kernel<1>, grid, dim3(THREADS), h->lds_bytes, (hipStream_t)stream, h->a, *io,
-                           deterministic);
+    launch_tiles(actor_forward_kernel<1>, actor_forward_kernel<2>, h->mt, h->a.n, h->lds_bytes, stream, h->a, *io,
+                 deterministic);
     return hipGetLastError() == hipSuccess ? PGX_OK : pgx_set_error(PGX_E_HIP, "pgx_actor_forward: launch failed");
 }
 
 int pgx_actor_state(pgx_actor_handle h, uint64_t* step, void* stream) {
     if (!h || !step) return pgx_set_error(PGX_E_INVALID, "pgx_actor_state: null handle or step pointer");
-    unsigned long long v = 0;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess ||
-        hipMemcpy(&v, h->a.step, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
-        return pgx_set_error(PGX_E_HIP, "pgx_actor_state: device read failed");
-    *step = v;
-    return PGX_OK;
+    return read_word("pgx_actor_state", h->a.step, step, stream);
 }
 
 int pgx_actor_set_state(pgx_actor_handle h, uint64_t step, void* stream) {
     if (!h) return pgx_set_error(PGX_E_INVALID, "pgx_actor_set_state: null handle");
-    const unsigned long long v = step;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess ||
-        hipMemcpy(h->a.step, &v, sizeof(v), hipMemcpyHostToDevice) != hipSuccess)
-        return pgx_set_error(PGX_E_HIP, "pgx_actor_set_state: device write failed");
-    return PGX_OK;
+    return write_word("pgx_actor_set_state", h->a.step, step, stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 /*
- * pgx_actor_host.cpp -- the Actor's argument checks and the host model of its arithmetic.
+ * pgx_actor_host.cpp -- the policy units' argument checks and the host models of their arithmetic.
  *
  * pgx_actor_forward_host restates, in plain C++ on host arrays, what pgx_actor.hip's forward kernel
  * computes up to the squash: the feature order, every Linear as one k-ordered std::fmaf chain that
@@ -7,8 +7,9 @@
  * ReLU, clip_mean and the log_std clamp.  On gfx950 the f32-input MFMA is such a chain bit for
  * bit, so the kernel is tested against this on the device and this against an independent
  * restatement on a CPU.  Never touches a device; the Actor does not step through it.
- * pgx_ac_forward_host (below) is the same for pgx_actor_critic.hip: both trunks and heads of the
- * ActorCritic over the same `linear`.
+ * pgx_ac_forward_host and pgx_sde_actor_forward_host (below) are the same for pgx_actor_critic.hip and
+ * pgx_sde_actor.hip, over the same `stage_x`, `hidden_layers` and `linear`; the three check_config share
+ * `check_common`, `check_count` and `check_widths`.
  */
 #include <cmath>
 #include <cstdint>
@@ -19,24 +20,51 @@
 
 int pgx_set_error(int code, const char* msg);  /* pgx_api.cpp: sets pgx_last_error() */
 
+namespace {
+
+int bad(const char* what, const char* field, const char* rest = "") {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: %s%s", what, field, rest);
+    return pgx_set_error(PGX_E_INVALID, msg);
+}
+
+/* what the three configs share */
+template <class Config>
+int check_common(const Config* c, const char* what, bool with_envs) {
+    if (!c) return bad(what, "null config");
+    if (with_envs && c->n_envs <= 0) return bad(what, "n_envs must be > 0");
+    if (c->obs_dim <= 0 || c->obs_dim > 4096) return bad(what, "obs_dim must be in 1..4096");
+    if (c->action_dim < 1 || c->action_dim > PGX_ACTOR_MAX_ACTION) return bad(what, "action_dim must be in 1..7");
+    return PGX_OK;
+}
+
+/* a stack's layer count, then its widths; `name` is the config field's */
+int check_count(const char* what, const char* name, int n) {
+    return n < 1 || n > PGX_ACTOR_MAX_LAYERS ? bad(what, name, " must be in 1..3") : PGX_OK;
+}
+
+int check_widths(const char* what, const char* name, int n, const int32_t* widths) {
+    for (int l = 0; l < n; l++)
+        if (widths[l] < 1 || widths[l] > PGX_ACTOR_MAX_WIDTH) return bad(what, name, " widths must be in 1..512");
+    return PGX_OK;
+}
+
+int check_clip_mean(const char* what, double clip_mean) {
+    return !(clip_mean >= 0.0) || std::isinf(clip_mean) ? bad(what, "clip_mean must be finite and >= 0") : PGX_OK;
+}
+
+}  // namespace
+
 /* pgx_actor_create's checks (no device call); `what` names the entry point */
 int pgx_actor_check_config(const pgx_actor_config* c, const char* what, bool with_envs) {
-    char msg[160];
-    auto bad = [&](const char* field) {
-        snprintf(msg, sizeof(msg), "%s: %s", what, field);
-        return pgx_set_error(PGX_E_INVALID, msg);
-    };
-    if (!c) return bad("null config");
-    if (with_envs && c->n_envs <= 0) return bad("n_envs must be > 0");
-    if (c->obs_dim <= 0 || c->obs_dim > 4096) return bad("obs_dim must be in 1..4096");
-    if (c->action_dim < 1 || c->action_dim > PGX_ACTOR_MAX_ACTION) return bad("action_dim must be in 1..7");
-    if (c->n_layers < 1 || c->n_layers > PGX_ACTOR_MAX_LAYERS) return bad("n_layers must be in 1..3");
-    for (int l = 0; l < c->n_layers; l++)
-        if (c->hidden[l] < 1 || c->hidden[l] > PGX_ACTOR_MAX_WIDTH) return bad("hidden widths must be in 1..512");
-    if (c->kind != PGX_ACTOR_GAUSSIAN && c->kind != PGX_ACTOR_DETERMINISTIC) return bad("unknown kind");
-    if (!(c->clip_mean >= 0.0) || std::isinf(c->clip_mean)) return bad("clip_mean must be finite and >= 0");
-    if (!(c->noise_sigma >= 0.0) || std::isinf(c->noise_sigma)) return bad("noise_sigma must be finite and >= 0");
-    if (!std::isfinite(c->noise_mu)) return bad("noise_mu must be finite");
+    int rc = check_common(c, what, with_envs);
+    if (rc == PGX_OK) rc = check_count(what, "n_layers", c->n_layers);
+    if (rc == PGX_OK) rc = check_widths(what, "hidden", c->n_layers, c->hidden);
+    if (rc != PGX_OK) return rc;
+    if (c->kind != PGX_ACTOR_GAUSSIAN && c->kind != PGX_ACTOR_DETERMINISTIC) return bad(what, "unknown kind");
+    if ((rc = check_clip_mean(what, c->clip_mean)) != PGX_OK) return rc;
+    if (!(c->noise_sigma >= 0.0) || std::isinf(c->noise_sigma)) return bad(what, "noise_sigma must be finite and >= 0");
+    if (!std::isfinite(c->noise_mu)) return bad(what, "noise_mu must be finite");
     return PGX_OK;
 }
 
@@ -51,6 +79,29 @@ void linear(const float* W, const float* b, const float* x, int K, int out, bool
         for (int k = K; k < K16; k++) acc = std::fmaf(0.0f, 0.0f, acc);
         y[o] = relu ? (acc > 0.0f ? acc : 0.0f) : acc;
     }
+}
+
+/* x [od + 6] = achieved_goal | desired_goal | observation of row e */
+void stage_x(float* x, const float* obs, const float* achieved_goal, const float* desired_goal, size_t e, int od) {
+    for (int k = 0; k < 3; k++) x[k] = achieved_goal[e * 3 + k];
+    for (int k = 0; k < 3; k++) x[3 + k] = desired_goal[e * 3 + k];
+    for (int k = 0; k < od; k++) x[6 + k] = obs[e * od + k];
+}
+
+/* the nl hidden Linears with their ReLU over x [in_dim], y and z taking turns as output; returns the
+ * last one's output, [hidden[nl - 1]] */
+const float* hidden_layers(int nl, const int32_t* hidden, const float* const* W, const float* const* b, const float* x,
+                           int in_dim, float* y, float* z) {
+    const float* in = x;
+    int K = in_dim;
+    float* out = y;
+    for (int l = 0; l < nl; l++) {
+        linear(W[l], b[l], in, K, hidden[l], true, out);
+        in = out;
+        K = hidden[l];
+        out = out == y ? z : y;
+    }
+    return in;
 }
 
 }  // namespace
@@ -70,19 +121,10 @@ extern "C" int pgx_actor_forward_host(const pgx_actor_config* cfg, const pgx_act
             return pgx_set_error(PGX_E_INVALID, "pgx_actor_forward_host: null weight or bias pointer");
     const float clip = (float)cfg->clip_mean;
     std::vector<float> x(od + 6), y(PGX_ACTOR_MAX_WIDTH), z(PGX_ACTOR_MAX_WIDTH);
+    const int K = cfg->hidden[nl - 1];
     for (int32_t e = 0; e < n; e++) {
-        for (int k = 0; k < 3; k++) x[k] = achieved_goal[(size_t)e * 3 + k];
-        for (int k = 0; k < 3; k++) x[3 + k] = desired_goal[(size_t)e * 3 + k];
-        for (int k = 0; k < od; k++) x[6 + k] = obs[(size_t)e * od + k];
-        const float* in = x.data();
-        int K = od + 6;
-        float* out = y.data();
-        for (int l = 0; l < nl; l++) {
-            linear(w->weight[l], w->bias[l], in, K, cfg->hidden[l], true, out);
-            in = out;
-            K = cfg->hidden[l];
-            out = out == y.data() ? z.data() : y.data();
-        }
+        stage_x(x.data(), obs, achieved_goal, desired_goal, (size_t)e, od);
+        const float* in = hidden_layers(nl, cfg->hidden, w->weight, w->bias, x.data(), od + 6, y.data(), z.data());
         float head[PGX_ACTOR_MAX_ACTION];
         linear(w->weight[nl], w->bias[nl], in, K, A, false, head);
         for (int d = 0; d < A; d++) {
@@ -106,22 +148,12 @@ extern "C" int pgx_actor_forward_host(const pgx_actor_config* cfg, const pgx_act
 
 /* pgx_ac_create's checks (no device call); `what` names the entry point */
 int pgx_ac_check_config(const pgx_ac_config* c, const char* what, bool with_envs) {
-    char msg[160];
-    auto bad = [&](const char* field) {
-        snprintf(msg, sizeof(msg), "%s: %s", what, field);
-        return pgx_set_error(PGX_E_INVALID, msg);
-    };
-    if (!c) return bad("null config");
-    if (with_envs && c->n_envs <= 0) return bad("n_envs must be > 0");
-    if (c->obs_dim <= 0 || c->obs_dim > 4096) return bad("obs_dim must be in 1..4096");
-    if (c->action_dim < 1 || c->action_dim > PGX_ACTOR_MAX_ACTION) return bad("action_dim must be in 1..7");
-    if (c->n_pi_layers < 1 || c->n_pi_layers > PGX_ACTOR_MAX_LAYERS) return bad("n_pi_layers must be in 1..3");
-    if (c->n_vf_layers < 1 || c->n_vf_layers > PGX_ACTOR_MAX_LAYERS) return bad("n_vf_layers must be in 1..3");
-    for (int l = 0; l < c->n_pi_layers; l++)
-        if (c->pi_hidden[l] < 1 || c->pi_hidden[l] > PGX_ACTOR_MAX_WIDTH) return bad("pi_hidden widths must be in 1..512");
-    for (int l = 0; l < c->n_vf_layers; l++)
-        if (c->vf_hidden[l] < 1 || c->vf_hidden[l] > PGX_ACTOR_MAX_WIDTH) return bad("vf_hidden widths must be in 1..512");
-    return PGX_OK;
+    int rc = check_common(c, what, with_envs);
+    if (rc == PGX_OK) rc = check_count(what, "n_pi_layers", c->n_pi_layers);
+    if (rc == PGX_OK) rc = check_count(what, "n_vf_layers", c->n_vf_layers);
+    if (rc == PGX_OK) rc = check_widths(what, "pi_hidden", c->n_pi_layers, c->pi_hidden);
+    if (rc == PGX_OK) rc = check_widths(what, "vf_hidden", c->n_vf_layers, c->vf_hidden);
+    return rc;
 }
 
 extern "C" int pgx_ac_forward_host(const pgx_ac_config* cfg, const pgx_ac_weights* w, const float* obs,
@@ -145,21 +177,11 @@ extern "C" int pgx_ac_forward_host(const pgx_ac_config* cfg, const pgx_ac_weight
     /* one trunk and its head over x: out_dim outputs into head */
     auto trunk = [&](int nl, const int32_t* hidden, const float* const* W, const float* const* b, const float* hw,
                      const float* hb, int out_dim, float* head) {
-        const float* in = x.data();
-        int K = od + 6;
-        float* out = y.data();
-        for (int l = 0; l < nl; l++) {
-            linear(W[l], b[l], in, K, hidden[l], true, out);
-            in = out;
-            K = hidden[l];
-            out = out == y.data() ? z.data() : y.data();
-        }
-        linear(hw, hb, in, K, out_dim, false, head);
+        const float* in = hidden_layers(nl, hidden, W, b, x.data(), od + 6, y.data(), z.data());
+        linear(hw, hb, in, hidden[nl - 1], out_dim, false, head);
     };
     for (int32_t e = 0; e < n; e++) {
-        for (int k = 0; k < 3; k++) x[k] = achieved_goal[(size_t)e * 3 + k];
-        for (int k = 0; k < 3; k++) x[3 + k] = desired_goal[(size_t)e * 3 + k];
-        for (int k = 0; k < od; k++) x[6 + k] = obs[(size_t)e * od + k];
+        stage_x(x.data(), obs, achieved_goal, desired_goal, (size_t)e, od);
         float head[PGX_ACTOR_MAX_ACTION];
         if (mean_out) {
             trunk(cfg->n_pi_layers, cfg->pi_hidden, w->pi_weight, w->pi_bias, w->action_net_weight, w->action_net_bias, A,
@@ -179,20 +201,11 @@ extern "C" int pgx_ac_forward_host(const pgx_ac_config* cfg, const pgx_ac_weight
 
 /* pgx_sde_actor_create's checks (no device call); `what` names the entry point */
 int pgx_sde_actor_check_config(const pgx_sde_actor_config* c, const char* what, bool with_envs) {
-    char msg[160];
-    auto bad = [&](const char* field) {
-        snprintf(msg, sizeof(msg), "%s: %s", what, field);
-        return pgx_set_error(PGX_E_INVALID, msg);
-    };
-    if (!c) return bad("null config");
-    if (with_envs && c->n_envs <= 0) return bad("n_envs must be > 0");
-    if (c->obs_dim <= 0 || c->obs_dim > 4096) return bad("obs_dim must be in 1..4096");
-    if (c->action_dim < 1 || c->action_dim > PGX_ACTOR_MAX_ACTION) return bad("action_dim must be in 1..7");
-    if (c->n_layers < 1 || c->n_layers > PGX_ACTOR_MAX_LAYERS) return bad("n_layers must be in 1..3");
-    for (int l = 0; l < c->n_layers; l++)
-        if (c->hidden[l] < 1 || c->hidden[l] > PGX_ACTOR_MAX_WIDTH) return bad("hidden widths must be in 1..512");
-    if (!(c->clip_mean >= 0.0) || std::isinf(c->clip_mean)) return bad("clip_mean must be finite and >= 0");
-    return PGX_OK;
+    int rc = check_common(c, what, with_envs);
+    if (rc == PGX_OK) rc = check_count(what, "n_layers", c->n_layers);
+    if (rc == PGX_OK) rc = check_widths(what, "hidden", c->n_layers, c->hidden);
+    if (rc == PGX_OK) rc = check_clip_mean(what, c->clip_mean);
+    return rc;
 }
 
 extern "C" int pgx_sde_actor_forward_host(const pgx_sde_actor_config* cfg, const pgx_sde_actor_weights* w,
@@ -213,19 +226,8 @@ extern "C" int pgx_sde_actor_forward_host(const pgx_sde_actor_config* cfg, const
     const float clip = (float)cfg->clip_mean;
     std::vector<float> x(od + 6), y(PGX_ACTOR_MAX_WIDTH), z(PGX_ACTOR_MAX_WIDTH);
     for (int32_t e = 0; e < n; e++) {
-        for (int k = 0; k < 3; k++) x[k] = achieved_goal[(size_t)e * 3 + k];
-        for (int k = 0; k < 3; k++) x[3 + k] = desired_goal[(size_t)e * 3 + k];
-        for (int k = 0; k < od; k++) x[6 + k] = obs[(size_t)e * od + k];
-        const float* in = x.data();
-        int K = od + 6;
-        float* out = y.data();
-        for (int l = 0; l < nl; l++) {
-            linear(w->weight[l], w->bias[l], in, K, cfg->hidden[l], true, out);
-            in = out;
-            K = cfg->hidden[l];
-            out = out == y.data() ? z.data() : y.data();
-        }
-        const float* latent = in;
+        stage_x(x.data(), obs, achieved_goal, desired_goal, (size_t)e, od);
+        const float* latent = hidden_layers(nl, cfg->hidden, w->weight, w->bias, x.data(), od + 6, y.data(), z.data());
         if (latent_out)
             for (int h = 0; h < H; h++) latent_out[(size_t)e * H + h] = latent[h];
         if (mean_out) {

@@ -1,5 +1,8 @@
 /*
- * pgx_common.h -- device helpers shared by the env-step kernels and the HER ring.
+ * pgx_common.h -- device helpers shared by the env-step kernels (pgx_kernels.hip), the HER ring
+ * (pgx_her.hip) and, through pgx_mlp.h, the policy units (pgx_actor.hip, pgx_actor_critic.hip,
+ * pgx_sde_actor.hip), which use philox.  Ends with fp contraction on: what follows an include of this
+ * header compiles in that state.
  */
 #pragma once
 #include <hip/hip_runtime.h>

@@ -5,7 +5,8 @@
  * include/pgx.h, section "SdeActor".
  *
  * Forward kernel: the Actor's workgroup (pgx_actor.hip) -- 4 waves own a tile of 16 (or 32) envs,
- * activations stay in LDS, every Linear is pgx_mlp.h's MFMA chain.  After the last trunk layer the
+ * activations stay in LDS; the staging, the Linear and the loop over the trunk's layers are pgx_mlp.h's,
+ * the host-side plan, allocation and packing pgx_policy.h's.  After the last trunk layer the
  * latent lies in LDS; wave 0 runs the mu head tile while the lanes that own an (env, a) pair, dealt
  * from wave 3 downwards, run the noise chain: H dependent fmaf on the latent (one 16-byte LDS read
  * per four h) against the env's matrix, streamed from global memory as one 16-byte load per lane per
@@ -18,29 +19,19 @@
  * are, transposed, exactly the 4 A floats of that env's h block.  The A lanes of one (env, h block)
  * exchange them through LDS, so every lane stores the one contiguous 16 bytes it owns.
  */
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <cstdlib>
+#include "pgx_policy.h"   /* pgx_mlp.h, pgx_common.h, include/pgx.h */
 
-#include "../../include/pgx.h"
-#include "pgx_common.h"
-#include "pgx_mlp.h"   /* linear_layer, pack_kernel, WAVES, NACC, f32x4 */
-
-int pgx_set_error(int code, const char* msg);  /* pgx_api.cpp: sets pgx_last_error() */
 int pgx_sde_actor_check_config(const pgx_sde_actor_config* c, const char* what, bool with_envs);  /* pgx_actor_host.cpp */
 
 namespace {
 
-constexpr int THREADS = 64 * WAVES;
-constexpr int MAX_LINEAR = PGX_ACTOR_MAX_LAYERS + 1;   /* the hidden layers and the mu tile */
 constexpr int PF = 4;                                  /* 16-byte matrix loads in flight per lane */
 
 struct SdeArgs {
-    int32_t n, od, ad, n_linear, S, H, H4;   /* S: LDS row stride (floats); H4: h blocks of 4 */
+    int32_t n, od, ad, S, H, H4;   /* S: LDS row stride (floats); H4: h blocks of 4 */
     float clip;
     uint32_t seed_lo, seed_hi;
-    int32_t nkb[MAX_LINEAR], ntiles[MAX_LINEAR];   /* 16-wide k blocks and output tiles per Linear */
-    int32_t woff[MAX_LINEAR], boff[MAX_LINEAR];    /* packed weights / padded bias, floats into params */
+    MlpPlan plan;                  /* the trunk and the mu tile */
     const float* params;
     float* E;                  /* the matrices, storage layout */
     float* std;                /* [H, A] */
@@ -59,35 +50,20 @@ __global__ __launch_bounds__(THREADS) void sde_forward_kernel(SdeArgs a, pgx_sde
     extern __shared__ float lds[];
     constexpr int ROWS = MT * 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int S = a.S, N = a.n, od = a.od, A = a.ad, H = a.H;
+    const int S = a.S, N = a.n, od = a.od, A = a.ad;
     const int env0 = blockIdx.x * ROWS;
-    /* features: achieved_goal | desired_goal | observation, +0 past in_dim and past env N */
-    const int K0 = a.nkb[0] * 16, in_dim = od + 6;
-    for (int idx = tid; idx < ROWS * K0; idx += THREADS) {
-        const int r = idx / K0, k = idx - r * K0;
-        const int e = env0 + r;
-        float v = 0.0f;
-        if (e < N && k < in_dim) {
-            if (k < 3) v = io.achieved_goal[(size_t)e * 3 + k];
-            else if (k < 6) v = io.desired_goal[(size_t)e * 3 + (k - 3)];
-            else v = io.obs[(size_t)e * od + (k - 6)];
-        }
-        lds[r * S + k] = v;
-    }
+    stage_features<MT>(lds, io.obs, io.achieved_goal, io.desired_goal, env0, N, od, a.plan.nkb[0] * 16, S, tid);
     __syncthreads();
-    int in_off = 0, out_off = ROWS * S;
-    for (int l = 0; l + 1 < a.n_linear; l++) {
-        linear_layer<MT>(lds, in_off, out_off, a.params + a.woff[l], a.params + a.boff[l], a.nkb[l], a.ntiles[l], S, true,
-                         lane, wave);
-        __syncthreads();
-        const int t = in_off;
-        in_off = out_off;
-        out_off = t;
-    }
-    /* the latent lies at lds[in_off]; the mu tile goes to lds[out_off] (one tile: wave 0) */
-    const int lm = a.n_linear - 1;
-    linear_layer<MT>(lds, in_off, out_off, a.params + a.woff[lm], a.params + a.boff[lm], a.nkb[lm], 1, S, false, lane, wave);
+    /* the trunk, every layer with its ReLU: the features lie in region 0; it and region ROWS * S take turns */
+    const int lm = a.plan.n_linear - 1;
+    const int in_off = run_linears<MT>(lds, a.params, a.plan, lm, true, 0, S, ROWS * S, 0, S, lane, wave);
+    const int out_off = in_off == 0 ? ROWS * S : 0;
+    /* the latent lies at lds[in_off]; the mu tile goes to lds[out_off] (one tile: wave 0), and no barrier
+     * stands between it and the noise chain */
+    linear_layer<MT>(lds, in_off, out_off, a.params + a.plan.woff[lm], a.params + a.plan.boff[lm], a.plan.nkb[lm], 1, S,
+                     false, lane, wave);
     /* the noise chain: pair p = r A + a, dealt from wave 3 downwards */
+    const int H = a.H;
     const int p = (WAVES - 1 - wave) * 64 + lane;
     const int r = p / A, d = p - r * A;
     const int e = env0 + r;
@@ -143,7 +119,7 @@ __global__ __launch_bounds__(THREADS) void sde_reset_kernel(SdeArgs a, int KB, f
     __shared__ float sh[THREADS * 4];
     __shared__ unsigned long long sh_gen;
     const int tid = threadIdx.x, A = a.ad, H = a.H, H4 = a.H4;
-    if (tid == 0) sh_gen = *a.gen;
+    load_word(&sh_gen, a.gen, true, tid);
     __syncthreads();
     const int i = tid % A, r = (tid / A) & 15, hbl = tid / (16 * A);
     const int hb = blockIdx.x * KB + hbl, tile = blockIdx.y;
@@ -157,9 +133,8 @@ __global__ __launch_bounds__(THREADS) void sde_reset_kernel(SdeArgs a, int KB, f
         float eps[4];
 #pragma unroll
         for (int c = 0; c < 2; c++) {
-            const float u1 = (float)((rr[2 * c] >> 8) + 1u) * 5.9604644775390625e-8f;
-            const float u2 = (float)(rr[2 * c + 1] >> 8) * 5.9604644775390625e-8f;
-            const float rad = sqrtf(-2.0f * logf(u1)), ang = 6.2831855f * u2;
+            float rad, ang;
+            box_muller(rr[2 * c], rr[2 * c + 1], &rad, &ang);
             eps[2 * c] = rad * cosf(ang);
             eps[2 * c + 1] = rad * sinf(ang);
         }
@@ -187,15 +162,7 @@ __global__ __launch_bounds__(THREADS) void sde_reset_kernel(SdeArgs a, int KB, f
         const size_t g = ((size_t)tile * H4 + hb) * 16 * A + r * A + i;
         reinterpret_cast<f32x4*>(a.E)[g] = *reinterpret_cast<const f32x4*>(sh + tid * 4);
     }
-    /* every workgroup has read the generation word (ahead of its first barrier): the last one to
-     * arrive moves it on */
-    if (tid == 0) {
-        __threadfence();
-        if (atomicAdd(a.ticket, 1u) == gridDim.x * gridDim.y - 1) {
-            *a.ticket = 0u;
-            *a.gen = sh_gen + 1ull;
-        }
-    }
+    advance_word(a.gen, a.ticket, &sh_gen, gridDim.x * gridDim.y, true, tid);
 }
 
 /* SB3's [N, H, A] <-> the storage layout, one thread per element */
@@ -224,8 +191,7 @@ struct pgx_sde_actor {
     int device;
     pgx_sde_actor_config cfg;
     SdeArgs a;
-    void* blob;
-    float* params;              /* packed weights and padded biases */
+    float* params;              /* packed weights and padded biases; the head of the one allocation */
     float* plain;               /* the parameters as given, torch layout; log_std last */
     size_t plain_w[4], plain_b[4], plain_ls;
     int mt;                     /* env tiles of 16 per workgroup */
@@ -233,28 +199,10 @@ struct pgx_sde_actor {
     size_t lds_bytes;
 };
 
-namespace {
-
-constexpr size_t LDS_LIMIT = 160 * 1024;
-
-/* (out, in) of parameter slot i: the hidden layers, mu */
-void slot_dims(const pgx_sde_actor_config& c, int i, int* out, int* in) {
-    const int nl = c.n_layers;
-    if (i < nl) {
-        *out = c.hidden[i];
-        *in = i == 0 ? c.obs_dim + 6 : c.hidden[i - 1];
-    } else {
-        *out = c.action_dim;
-        *in = c.hidden[nl - 1];
-    }
-}
-
-}  // namespace
-
 extern "C" {
 
 int pgx_sde_actor_create(const pgx_sde_actor_config* cfg, int device, pgx_sde_actor_handle* out) {
-    const int rc = pgx_sde_actor_check_config(cfg, "pgx_sde_actor_create", true);
+    int rc = pgx_sde_actor_check_config(cfg, "pgx_sde_actor_create", true);
     if (rc != PGX_OK) return rc;
     if (!out) return pgx_set_error(PGX_E_INVALID, "pgx_sde_actor_create: null handle pointer");
     *out = nullptr;
@@ -266,76 +214,41 @@ int pgx_sde_actor_create(const pgx_sde_actor_config* cfg, int device, pgx_sde_ac
     a.n = cfg->n_envs;
     a.od = cfg->obs_dim;
     a.ad = cfg->action_dim;
-    a.n_linear = nl + 1;
     a.H = cfg->hidden[nl - 1];
     a.H4 = (a.H + 3) / 4;
     a.clip = (float)cfg->clip_mean;
     a.seed_lo = (uint32_t)cfg->seed;
     a.seed_hi = (uint32_t)(cfg->seed >> 32);
-    size_t off = 0;
-    int widest = 16;
-    for (int l = 0; l <= nl; l++) {
-        int o, in;
-        slot_dims(*cfg, l, &o, &in);
-        a.nkb[l] = (in + 15) / 16;
-        a.ntiles[l] = l < nl ? (o + 15) / 16 : 1;
-        a.woff[l] = (int32_t)off;
-        off += (size_t)a.nkb[l] * a.ntiles[l] * 256;
-        a.boff[l] = (int32_t)off;
-        off += (size_t)a.ntiles[l] * 16;
-        if (a.nkb[l] * 16 > widest) widest = a.nkb[l] * 16;
-    }
-    a.S = widest + 4;
-    const size_t n_params = off;
-    size_t n_plain = 0;
-    for (int i = 0; i <= nl; i++) {
-        int o, in;
-        slot_dims(*cfg, i, &o, &in);
-        h->plain_w[i] = n_plain;
-        n_plain += (size_t)o * in;
-        h->plain_b[i] = n_plain;
-        n_plain += (size_t)o;
-    }
+    size_t n_params = 0, n_plain = 0;
+    a.S = 4 + plan_stack(&a.plan, cfg->obs_dim + 6, cfg->hidden, nl, cfg->action_dim, 0, &n_params, h->plain_w,
+                         h->plain_b, &n_plain);
     h->plain_ls = n_plain;
     const size_t n_std = (size_t)a.H * a.ad;
     n_plain += n_std;
-    /* 32 envs per workgroup from 4096 envs on, as the Actor */
-    h->mt = cfg->n_envs >= 4096 ? 2 : 1;
-    if (2 * (size_t)h->mt * 16 * a.S * 4 > LDS_LIMIT) h->mt = 1;
-    h->lds_bytes = 2 * (size_t)h->mt * 16 * a.S * 4;
-    if (h->lds_bytes > LDS_LIMIT) {
+    /* the tile as the Actor chooses it, without an override */
+    auto lds_need = [&a](int mt) { return 2 * (size_t)mt * 16 * a.S * 4; };
+    h->mt = choose_tile(cfg->n_envs, nullptr, lds_need);
+    if (h->mt == 0) {
         delete h;
         return pgx_set_error(PGX_E_UNSUPPORTED, "pgx_sde_actor_create: obs_dim too wide for the activations in LDS");
     }
+    h->lds_bytes = lds_need(h->mt);
     h->kb = THREADS / (16 * a.ad);
-    if (hipSetDevice(device) != hipSuccess) {
-        delete h;
-        return pgx_set_error(PGX_E_HIP, "pgx_sde_actor_create: hipSetDevice");
-    }
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t tiles = ((size_t)cfg->n_envs + 15) / 16;
-    const size_t n_E = tiles * a.H4 * 16 * a.ad * 4;
-    const size_t o_plain = al(n_params * 4), o_std = al(o_plain + n_plain * 4), o_E = al(o_std + n_std * 4),
-                 o_words = al(o_E + n_E * 4), total = o_words + 256;
-    if (hipMalloc(&h->blob, total) != hipSuccess) {
-        delete h;
-        return pgx_set_error(PGX_E_NOMEM, "pgx_sde_actor_create: hipMalloc failed");
-    }
+    const size_t bytes[5] = {n_params * 4, n_plain * 4, n_std * 4, tiles * a.H4 * 16 * a.ad * 4 * 4, 256};
+    void* ptr[5];
     const void* fn = h->mt == 2 ? (const void*)sde_forward_kernel<2> : (const void*)sde_forward_kernel<1>;
-    if (hipMemset(h->blob, 0, total) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes) != hipSuccess) {
-        (void)hipFree(h->blob);
+    rc = create_blob("pgx_sde_actor_create", device, bytes, 5, ptr, {fn}, h->lds_bytes);
+    if (rc != PGX_OK) {
         delete h;
-        return pgx_set_error(PGX_E_HIP, "pgx_sde_actor_create: device setup failed");
+        return rc;
     }
-    char* b = (char*)h->blob;
-    h->params = (float*)b;
-    h->plain = (float*)(b + o_plain);
-    a.params = h->params;
-    a.std = (float*)(b + o_std);
-    a.E = (float*)(b + o_E);
-    a.gen = (unsigned long long*)(b + o_words);
-    a.ticket = (uint32_t*)(b + o_words + 8);
+    a.params = h->params = (float*)ptr[0];
+    h->plain = (float*)ptr[1];
+    a.std = (float*)ptr[2];
+    a.E = (float*)ptr[3];
+    a.gen = (unsigned long long*)ptr[4];
+    a.ticket = (uint32_t*)((char*)ptr[4] + 8);
     *out = h;
     return PGX_OK;
 }
@@ -343,7 +256,7 @@ int pgx_sde_actor_create(const pgx_sde_actor_config* cfg, int device, pgx_sde_ac
 void pgx_sde_actor_destroy(pgx_sde_actor_handle h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    (void)hipFree(h->blob);
+    (void)hipFree(h->params);
     delete h;
 }
 
@@ -355,17 +268,13 @@ int pgx_sde_actor_set_weights(pgx_sde_actor_handle h, const pgx_sde_actor_weight
             return pgx_set_error(PGX_E_INVALID, "pgx_sde_actor_set_weights: null weight or bias pointer");
     if (!w->log_std) return pgx_set_error(PGX_E_INVALID, "pgx_sde_actor_set_weights: null log_std pointer");
     hipStream_t st = (hipStream_t)stream;
+    const MlpPlan& p = h->a.plan;
     for (int i = 0; i <= nl; i++) {
         int o, in;
-        slot_dims(h->cfg, i, &o, &in);
-        float* pw = h->plain + h->plain_w[i];
-        float* pb = h->plain + h->plain_b[i];
-        if (hipMemcpyAsync(pw, w->weight[i], (size_t)o * in * 4, hipMemcpyDefault, st) != hipSuccess ||
-            hipMemcpyAsync(pb, w->bias[i], (size_t)o * 4, hipMemcpyDefault, st) != hipSuccess)
+        linear_dims(h->cfg.obs_dim + 6, h->cfg.hidden, nl, h->cfg.action_dim, i, &o, &in);
+        if (!pack_linear(w->weight[i], w->bias[i], h->plain + h->plain_w[i], h->plain + h->plain_b[i], o, in,
+                         h->params + p.woff[i], h->params + p.boff[i], p.ntiles[i], 0, st))
             return pgx_set_error(PGX_E_HIP, "pgx_sde_actor_set_weights: copy failed");
-        const int n = o * in + o;
-        hipLaunchKernelGGL(pack_kernel, dim3((n + 255) / 256), dim3(256), 0, st, pw, pb, h->params + h->a.woff[i],
-                           h->params + h->a.boff[i], o, in, h->a.ntiles[i], 0);
     }
     const int n_std = h->a.H * h->a.ad;
     float* ls = h->plain + h->plain_ls;
@@ -388,34 +297,19 @@ int pgx_sde_actor_forward(pgx_sde_actor_handle h, const pgx_sde_actor_io* io, in
     if (!h || !io) return pgx_set_error(PGX_E_INVALID, "pgx_sde_actor_forward: null handle or io");
     if (!io->obs || !io->achieved_goal || !io->desired_goal || !io->action)
         return pgx_set_error(PGX_E_INVALID, "pgx_sde_actor_forward: null observation or action pointer");
-    const int rows = h->mt * 16;
-    const dim3 grid((h->a.n + rows - 1) / rows);
-    if (h->mt == 2)
-        hipLaunchKernelGGL(sde_forward_kernel<2>, grid, dim3(THREADS), h->lds_bytes, (hipStream_t)stream, h->a, *io,
-                           deterministic);
-    else
-        hipLaunchKernelGGL(sde_forward_kernel<1>, grid, dim3(THREADS), h->lds_bytes, (hipStream_t)stream, h->a, *io,
-                           deterministic);
+    launch_tiles(sde_forward_kernel<1>, sde_forward_kernel<2>, h->mt, h->a.n, h->lds_bytes, stream, h->a, *io,
+                 deterministic);
     return hipGetLastError() == hipSuccess ? PGX_OK : pgx_set_error(PGX_E_HIP, "pgx_sde_actor_forward: launch failed");
 }
 
 int pgx_sde_actor_state(pgx_sde_actor_handle h, uint64_t* generation, void* stream) {
     if (!h || !generation) return pgx_set_error(PGX_E_INVALID, "pgx_sde_actor_state: null handle or generation pointer");
-    unsigned long long v = 0;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess ||
-        hipMemcpy(&v, h->a.gen, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
-        return pgx_set_error(PGX_E_HIP, "pgx_sde_actor_state: device read failed");
-    *generation = v;
-    return PGX_OK;
+    return read_word("pgx_sde_actor_state", h->a.gen, generation, stream);
 }
 
 int pgx_sde_actor_set_state(pgx_sde_actor_handle h, uint64_t generation, void* stream) {
     if (!h) return pgx_set_error(PGX_E_INVALID, "pgx_sde_actor_set_state: null handle");
-    const unsigned long long v = generation;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess ||
-        hipMemcpy(h->a.gen, &v, sizeof(v), hipMemcpyHostToDevice) != hipSuccess)
-        return pgx_set_error(PGX_E_HIP, "pgx_sde_actor_set_state: device write failed");
-    return PGX_OK;
+    return write_word("pgx_sde_actor_set_state", h->a.gen, generation, stream);
 }
 
 int pgx_sde_actor_get_matrices(pgx_sde_actor_handle h, float* out, void* stream) {

@@ -18,21 +18,15 @@ The distribution's variance and ``log_prob``, critics and optimisers are trainin
 from __future__ import annotations
 
 import ctypes as C
-from typing import Any, Callable, Dict, List, Optional, Sequence
+from typing import Any, Callable, Dict, Optional, Sequence
 
 import numpy as np
 
 from . import abi
-from ._native import PgxError, check, load
-from .actor import OBS_KEYS
-
-try:
-    import torch
-except ImportError:  # pragma: no cover
-    torch = None
+from ._policy import Policy, torch
 
 
-class SdeActor:
+class SdeActor(Policy):
     """SB3's SAC / TQC actor with ``use_sde=True`` on the device.
 
     ``env``: a ``PandaVecEnv`` or a wrapper of one (``n_envs``, the dims and the device are read from it),
@@ -45,24 +39,12 @@ class SdeActor:
                  net_arch: Sequence[int] = (256, 256), log_std_init: float = -3.0, clip_mean: float = 2.0,
                  full_std: bool = True, use_expln: bool = False, seed: int = 0, device: Any = None,
                  n_envs: Optional[int] = None):
-        if torch is None:
-            raise PgxError("SdeActor needs torch for its buffers")
+        self._need_torch()
         if not full_std:
             raise ValueError("full_std=False is not built")
         if use_expln:
             raise ValueError("use_expln=True is not built")
-        if env is not None:
-            n_envs = env.num_envs
-            obs_dim = env.obs_dim if obs_dim is None else obs_dim
-            action_dim = env.action_dim if action_dim is None else action_dim
-            device = env.device if device is None else device
-        if obs_dim is None or action_dim is None or n_envs is None:
-            raise ValueError("pass env, or obs_dim, action_dim and n_envs")
-        if int(n_envs) <= 0:
-            raise ValueError("n_envs must be > 0")
-        self.lib = load()
-        self.device = torch.device("cuda:0" if device is None else device)
-        self.n_envs, self.obs_dim, self.action_dim = int(n_envs), int(obs_dim), int(action_dim)
+        self._resolve(env, obs_dim, action_dim, n_envs, device)
         self.net_arch = tuple(int(w) for w in net_arch)
         self.log_std_init, self.clip_mean, self.seed = float(log_std_init), float(clip_mean), int(seed)
         cfg = abi.PgxSdeActorConfig()
@@ -73,7 +55,6 @@ class SdeActor:
         cfg.clip_mean = self.clip_mean
         cfg.seed = self.seed & 0xFFFFFFFFFFFFFFFF
         self._cfg = cfg
-        self._h = None
         self.latent_dim = self.net_arch[min(len(self.net_arch), abi.ACTOR_MAX_LAYERS) - 1] if self.net_arch else 0
         # the parameters as given (torch layout), on the actor's device: what set_weights reads
         dims = [self.obs_dim + 6] + list(self.net_arch)
@@ -86,27 +67,11 @@ class SdeActor:
         self._log_std = torch.full((max(self.latent_dim, 0), self.action_dim), self.log_std_init, dtype=torch.float32,
                                    device=self.device)
         self.actions = torch.zeros((self.n_envs, self.action_dim), dtype=torch.float32, device=self.device)
-        self._debug: Optional[Dict[str, "torch.Tensor"]] = None
-        self._keep: List[Any] = []
-        if self.device.type == "cuda":
-            h = C.c_void_p()
-            torch.cuda.set_device(self.device)
-            check(self.lib.pgx_sde_actor_create(C.byref(cfg), self.device.index or 0, C.byref(h)), "pgx_sde_actor_create",
-                  self.lib)
-            self._h = h
-            self._push()
-        else:   # the library's argument checks either way: the host model on no rows
-            self.forward_host({"observation": np.zeros((0, self.obs_dim), np.float32),
-                               "achieved_goal": np.zeros((0, 3), np.float32), "desired_goal": np.zeros((0, 3), np.float32)},
-                              np.zeros((0, max(self.latent_dim, 0), self.action_dim), np.float32))
+        self._open(np.zeros((0, max(self.latent_dim, 0), self.action_dim), np.float32))
 
     # ------------------------------------------------------------ plumbing
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _need_device(self):
-        if self._h is None:
-            raise PgxError("this SdeActor has no device handle (device='cpu' or closed): no CPU fallback")
+    _PREFIX = "pgx_sde_actor"
+    _SD_PREFIX = "actor."
 
     def _weights_struct(self, ws, bs, log_std) -> abi.PgxSdeActorWeights:
         w = abi.PgxSdeActorWeights()
@@ -117,60 +82,26 @@ class SdeActor:
 
     def _push(self) -> None:
         w = self._weights_struct([t.data_ptr() for t in self._w], [t.data_ptr() for t in self._b], self._log_std.data_ptr())
-        check(self.lib.pgx_sde_actor_set_weights(self._h, C.byref(w), self._stream()), "pgx_sde_actor_set_weights", self.lib)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            torch.cuda.synchronize(self.device)
-            self.lib.pgx_sde_actor_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._lib_call("set_weights", self._h, C.byref(w), self._stream())
 
     # ----------------------------------------------------------- parameters
     def _slots(self):
         """(key, tensor) of every parameter in SB3's order."""
-        out = []
-        for name, w, b in zip(self._names, self._w, self._b):
-            out += [(f"{name}.weight", w), (f"{name}.bias", b)]
-        return out + [("log_std", self._log_std)]
-
-    def state_dict(self) -> Dict[str, "torch.Tensor"]:
-        """The parameters under SB3's actor key names (copies, on the actor's device)."""
-        return {k: t.clone() for k, t in self._slots()}
+        return self._pairs() + [("log_std", self._log_std)]
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
         """Load SB3 gSDE actor parameters: ``latent_pi.{0,2,4}``, ``mu.0`` (``mu`` with ``clip_mean == 0``),
         ``.weight`` [out, in] and ``.bias`` [out], and ``log_std`` [H, A]; a policy's state dict works too
         (its ``actor.`` keys are read, the rest ignored).  The packed weights and ``std`` in the handle are
         replaced on the current stream: a captured graph uses them at its next replay."""
-        if any(k.startswith("actor.") for k in sd):
-            sd = {k[len("actor."):]: v for k, v in sd.items() if k.startswith("actor.")}
-        new = []
-        for key, cur in self._slots():
-            if key not in sd:
-                raise KeyError(f"load_state_dict: missing key {key!r}")
-            v = sd[key]
-            t = v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
-            if tuple(t.shape) != tuple(cur.shape):
-                raise ValueError(f"load_state_dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(cur.shape)}")
-            new.append(t.to(device=self.device, dtype=torch.float32).contiguous())
-        for (_, cur), t in zip(self._slots(), new):
-            cur.copy_(t)   # in place: the handle's copies read these same buffers
-        if self._h is not None:
-            self._push()
+        self._load_slots(sd)   # validates every key, then copies
 
     @property
     def std(self) -> "torch.Tensor":
         """``exp(log_std)`` [H, A] as the handle holds it (a copy)."""
         self._need_device()
         out = torch.empty_like(self._log_std)
-        check(self.lib.pgx_sde_actor_get_std(self._h, C.c_void_p(out.data_ptr()), self._stream()), "pgx_sde_actor_get_std",
-              self.lib)
+        self._lib_call("get_std", self._h, C.c_void_p(out.data_ptr()), self._stream())
         return out
 
     # ----------------------------------------------------------------- noise
@@ -191,38 +122,24 @@ class SdeActor:
         self._need_device()
         d = self._debug
         e, p = (None, None) if d is None else (C.c_void_p(d["eps"].data_ptr()), C.c_void_p(d["philox"].data_ptr()))
-        check(self.lib.pgx_sde_actor_reset_noise(self._h, e, p, self._stream()), "pgx_sde_actor_reset_noise", self.lib)
+        self._lib_call("reset_noise", self._h, e, p, self._stream())
 
-    @property
-    def noise_generation(self) -> int:
-        """The device word that keys the matrix draw and counts the resamples (this synchronises).  Setting
-        it back reproduces the draws."""
-        self._need_device()
-        v = C.c_uint64(0)
-        check(self.lib.pgx_sde_actor_state(self._h, C.byref(v), self._stream()), "pgx_sde_actor_state", self.lib)
-        return int(v.value)
-
-    @noise_generation.setter
-    def noise_generation(self, value: int) -> None:
-        self._need_device()
-        check(self.lib.pgx_sde_actor_set_state(self._h, C.c_uint64(int(value) & 0xFFFFFFFFFFFFFFFF), self._stream()),
-              "pgx_sde_actor_set_state", self.lib)
+    noise_generation = property(Policy._get_word, Policy._set_word, doc="""The device word that keys the matrix draw
+        and counts the resamples (this synchronises).  Setting it back reproduces the draws.""")
 
     @property
     def exploration_matrices(self) -> "torch.Tensor":
         """The matrices [N, H, A] in SB3's layout (a copy; the handle keeps a layout of its own)."""
         self._need_device()
         out = torch.empty((self.n_envs, self.latent_dim, self.action_dim), dtype=torch.float32, device=self.device)
-        check(self.lib.pgx_sde_actor_get_matrices(self._h, C.c_void_p(out.data_ptr()), self._stream()),
-              "pgx_sde_actor_get_matrices", self.lib)
+        self._lib_call("get_matrices", self._h, C.c_void_p(out.data_ptr()), self._stream())
         return out
 
     @exploration_matrices.setter
     def exploration_matrices(self, value: Any) -> None:
         self._need_device()
         t = self._dev(value, (self.n_envs, self.latent_dim, self.action_dim))
-        check(self.lib.pgx_sde_actor_set_matrices(self._h, C.c_void_p(t.data_ptr()), self._stream()),
-              "pgx_sde_actor_set_matrices", self.lib)
+        self._lib_call("set_matrices", self._h, C.c_void_p(t.data_ptr()), self._stream())
         self._keep_m = t   # alive until the stream has consumed it
 
     # --------------------------------------------------------------- forward
@@ -231,14 +148,7 @@ class SdeActor:
         p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         io = abi.PgxSdeActorIo(p(obs["observation"]), p(obs["achieved_goal"]), p(obs["desired_goal"]), p(self.actions),
                                *([None] * 3 if d is None else [p(d[k]) for k in ("mean", "latent", "noise")]))
-        check(self.lib.pgx_sde_actor_forward(self._h, C.byref(io), 1 if deterministic else 0, self._stream()),
-              "pgx_sde_actor_forward", self.lib)
-
-    def _dev(self, x, shape) -> "torch.Tensor":
-        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-        if tuple(t.shape) != shape:
-            raise ValueError(f"expected shape {list(shape)}, got {list(t.shape)}")
-        return t.to(device=self.device, dtype=torch.float32).contiguous()   # a no-op for the env's own buffers
+        self._lib_call("forward", self._h, C.byref(io), 1 if deterministic else 0, self._stream())
 
     def __call__(self, obs: Dict[str, Any], deterministic: bool = False) -> "torch.Tensor":
         """Actions [N, A] for the observation dict ``obs`` (what ``step_tensors`` / ``reset_tensors`` of an
@@ -246,8 +156,7 @@ class SdeActor:
         ``tanh(mean)``, no matrix is read.  Returns the actor's persistent action tensor (overwritten by
         the next call)."""
         self._need_device()
-        N = self.n_envs
-        o = {k: self._dev(obs[k], (N, self.obs_dim if k == "observation" else 3)) for k in OBS_KEYS}
+        o = self._obs(obs)
         self._launch(o, deterministic)
         self._keep = [o]   # alive until the stream has consumed them
         return self.actions
@@ -257,22 +166,17 @@ class SdeActor:
     def forward_host(self, obs: Dict[str, Any], matrices: Any):
         """``(mean [n, A], latent [n, H], noise [n, A])`` numpy f32 from the library's host model of the
         kernel's arithmetic, for any number of rows and their ``matrices`` [n, H, A].  A test oracle."""
-        o = {k: np.ascontiguousarray(obs[k].cpu().numpy() if torch.is_tensor(obs[k]) else obs[k], dtype=np.float32)
-             for k in OBS_KEYS}
-        n = o["observation"].shape[0]
+        (o, n), (ws, bs) = self._host_obs(obs), self._host_params()
         H, A = max(self.latent_dim, 0), self.action_dim
         m = np.ascontiguousarray(matrices.cpu().numpy() if torch.is_tensor(matrices) else matrices, dtype=np.float32)
         if m.shape != (n, H, A):
             raise ValueError(f"expected matrices of shape {[n, H, A]}, got {list(m.shape)}")
-        ws = [np.ascontiguousarray(t.cpu().numpy()) for t in self._w]
-        bs = [np.ascontiguousarray(t.cpu().numpy()) for t in self._b]
         ls = np.ascontiguousarray(self._log_std.cpu().numpy())
         w = self._weights_struct([x.ctypes.data for x in ws], [x.ctypes.data for x in bs], ls.ctypes.data)
         mean, latent, noise = np.zeros((n, A), np.float32), np.zeros((n, H), np.float32), np.zeros((n, A), np.float32)
-        check(self.lib.pgx_sde_actor_forward_host(C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
-                                                  abi.ptr(o["achieved_goal"]), abi.ptr(o["desired_goal"]), abi.ptr(m), n,
-                                                  abi.ptr(mean), abi.ptr(latent), abi.ptr(noise)),
-              "pgx_sde_actor_forward_host", self.lib)
+        self._lib_call("forward_host", C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
+                       abi.ptr(o["achieved_goal"]), abi.ptr(o["desired_goal"]), abi.ptr(m), n, abi.ptr(mean),
+                       abi.ptr(latent), abi.ptr(noise))
         return mean, latent, noise
 
     # --------------------------------------------------------------- rollouts
@@ -281,12 +185,7 @@ class SdeActor:
 
         self._need_device()
         obs = step_buffers(venv)[0]
-        N = self.n_envs
-        for key in OBS_KEYS:
-            t = obs[key]
-            if tuple(t.shape) != (N, self.obs_dim if key == "observation" else 3) or t.dtype != torch.float32 \
-                    or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"venv's {key} buffer does not fit this actor")
+        self._check_venv_obs(obs)
         return obs
 
     def _enqueue_rollout(self, venv, obs, k: int, deterministic: bool, after_step, sde_sample_freq: int, what: str) -> None:
