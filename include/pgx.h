@@ -1282,6 +1282,154 @@ int pgx_sde_actor_forward_host(const pgx_sde_actor_config* cfg, const pgx_sde_ac
                                const float* achieved_goal, const float* desired_goal, const float* matrices, int32_t n,
                                float* mean_out, float* latent_out, float* noise_out);
 
+/* ----------------------------------------------------------------------
+ * QuantileCritic: sb3_contrib TQC's quantile critics on the device (pgx_quantile_critic.hip): the
+ * forward of `critic` or `critic_target` (tqc/policies.py, Critic.forward), the no_grad block of
+ * TQC.train that builds the truncated TD target (tqc/tqc.py) as one launch, and the Polyak step.  No
+ * gradient is computed here.  This is a restatement: neither library is importable where this is built,
+ * parity against them is not pinned by a test.
+ *
+ * Networks: n_critics independent nets qf0 .. qf{n-1}; each n_layers x (Linear + ReLU), widths
+ * hidden[l], then a Linear to n_quantiles outputs.  Features, K = obs_dim + 6 + action_dim:
+ *   x = achieved_goal[3] | desired_goal[3] | observation[obs_dim] | action[action_dim]
+ * (CombinedExtractor's order, then th.cat([obs, action], dim=1)).  quantiles [B, n_critics,
+ * n_quantiles] (th.stack(..., dim=1)).  The handle holds two parameter sets, PGX_QC_ONLINE (`critic`)
+ * and PGX_QC_TARGET (`critic_target`).
+ *
+ * Arithmetic contract of every Linear: the Actor's, word for word (above): acc = bias[o], then
+ * acc = fmaf(x[k], W[o][k], acc) for k = 0 .. K16 - 1 ascending, K16 = K rounded up to 16 with +0
+ * padding, one accumulator per output, no split of K; relu(v) = v > 0 ? v : +0.  The head spans
+ * ceil(n_quantiles / 16) output tiles.  pgx_qc_forward_host restates it; the kernel's
+ * v_mfma_f32_16x16x4_f32 meets it bit for bit.
+ *
+ * Truncated target (pgx_qc_target), T = n_critics * n_quantiles, per row b < B:
+ *   z[c * n_quantiles + q] = quantile q of critic c of the TARGET set on the row's features
+ *   sort z ascending by the ORDER RULE: element i precedes element j when key(z[i]) < key(z[j]), or
+ *     the keys are equal and i < j, where for the f32's bits u (uint32)
+ *       key(u) = u & 0x80000000 ? ~u : u | 0x80000000
+ *     compared as unsigned integers.  The order is total on all bit patterns: -inf < negative < -0 <
+ *     +0 < positive < +inf, equal bits by flat index; a NaN with the sign bit set sorts below -inf,
+ *     one without above +inf.  Every element gets exactly one of the ranks 0 .. T - 1.
+ *   keep the n_target lowest: z_(0) .. z_(n_target - 1)
+ *   then in f32, every operation rounded on its own (no contraction):
+ *     t1 = ent_coef * next_log_prob[b]
+ *     t2 = z_(k) - t1
+ *     m  = (1.0f - done[b]) * (float)gamma
+ *     out[b][k] = reward[b] + m * t2
+ *   (tqc.py: next_quantiles - ent_coef * next_log_prob.reshape(-1, 1); rewards + (1 - dones) * gamma *
+ *   target_quantiles, with (1 - dones) * gamma evaluated first as Python does).  Every out[b][k], k <
+ *   n_target, b < B, is written whatever the input bits; what a row with a NaN holds is outside the
+ *   contract; nothing else is written.  ent_coef is read from device memory (one float) at every
+ *   launch.  n_quantiles = 1, n_target = 1 is SAC's / TD3's min over the critics.
+ *
+ * Polyak (pgx_qc_polyak; SB3 polyak_update(critic.parameters(), critic_target.parameters(), tau)), on
+ * the handle's plain copies, per parameter element, in f32:
+ *     t = fmaf((float)tau, p, t * (float)(1.0 - tau))
+ * the product t * (float)(1.0 - tau) rounded first, 1.0 - tau taken in double; then the target set is
+ * packed again from its plain copy.  torch's kernel for mul_ / add_(alpha=) may round differently:
+ * parity of this rule with torch is not pinned.  pgx_qc_sync_target copies online -> target bit for
+ * bit (plain and packed).
+ *
+ * Packed weights: the Actor's P[kb][tile][lane][i] per Linear, per critic, per set.  A workgroup of 4
+ * waves owns 32 rows (16 for B <= 16, or where 32 do not fit the LDS) and runs the critics one after the other on
+ * features staged once; the pooled quantiles stay in LDS for the sort (rank by counting).  LDS per
+ * workgroup: 4 rows (max(K16 + 4 + 2 (H16 + 4), T4) + 16 n_critics ceil(n_quantiles / 16) + 4) bytes, H16
+ * the widest hidden width rounded up to 16, T4 = T rounded up to 4 (pgx_qc_create states the limit).
+ * Every entry below but create / destroy / get_weights enqueues kernel launches only on the caller's
+ * stream (no memcpy or memset node, no allocation, no sync), so everything captures as a single chain;
+ * pgx_qc_set_weights first copies the parameters into the handle (copy operations on `stream`).
+ * ---------------------------------------------------------------------- */
+typedef struct pgx_qc* pgx_qc_handle;
+
+#define PGX_QC_ONLINE 0          /* `critic` */
+#define PGX_QC_TARGET 1          /* `critic_target` */
+#define PGX_QC_MAX_CRITICS 5
+#define PGX_QC_MAX_QUANTILES 32
+#define PGX_QC_MAX_POOL 128      /* n_critics * n_quantiles at the most */
+
+typedef struct pgx_qc_config {
+    int32_t obs_dim;
+    int32_t action_dim;           /* 1..7 */
+    int32_t n_layers;             /* 1..3 hidden layers */
+    int32_t hidden[3];            /* widths of the first n_layers, 1..512 each */
+    int32_t n_critics;            /* 1..5 */
+    int32_t n_quantiles;          /* 1..32; n_critics * n_quantiles <= 128 */
+    double gamma;                 /* finite */
+} pgx_qc_config;
+
+/* torch-layout f32 parameters of one set, device or host pointers: for critic c, weight[c][l] [out, in]
+ * row-major and bias[c][l] [out] for the hidden layers l < n_layers, then the quantile head at index
+ * n_layers (state-dict keys qf{c}.{2 l}.weight / .bias). */
+typedef struct pgx_qc_weights {
+    const float* weight[5][4];
+    const float* bias[5][4];
+} pgx_qc_weights;
+
+/* Pointers of one launch (device for pgx_qc_forward / pgx_qc_target, host for the host models), each
+ * row-indexed input with its row stride in floats: row b of `obs` starts at obs + b * obs_stride.  A
+ * dense [B, width] tensor has stride = width; the fields of a HER batch's rows (pgx_replay_batch.rows)
+ * are read in place with stride = pgx_replay_row_stride.  pgx_qc_forward reads obs .. action and writes
+ * `out`; pgx_qc_target reads everything (obs .. action hold the NEXT observation and the next action). */
+typedef struct pgx_qc_io {
+    const float* obs;             /* [B,obs_dim] */
+    const float* achieved_goal;   /* [B,3] */
+    const float* desired_goal;    /* [B,3] */
+    const float* action;          /* [B,action_dim] */
+    const float* reward;          /* target: [B] */
+    const float* done;            /* target: [B], 0.0f or 1.0f */
+    const float* next_log_prob;   /* target: [B], dense */
+    const float* ent_coef;        /* target: one float */
+    float* out;                   /* forward: [B,n_critics,n_quantiles]; target: [B,n_target]; dense */
+    float* quantiles_out;         /* target: debug [B,n_critics,n_quantiles] or NULL: z before the sort */
+    int32_t obs_stride;           /* >= obs_dim */
+    int32_t achieved_goal_stride; /* >= 3 */
+    int32_t desired_goal_stride;  /* >= 3 */
+    int32_t action_stride;        /* >= action_dim */
+    int32_t reward_stride;        /* target: >= 1 */
+    int32_t done_stride;          /* target: >= 1 */
+} pgx_qc_io;
+
+/* tqc/policies.py, Critic.__init__ (both sets, parameters +0).  PGX_E_INVALID, before any device call and
+ * naming the field, for obs_dim outside 1..4096, action_dim outside 1..7, n_layers outside 1..3, a
+ * hidden width outside 1..512, n_critics outside 1..5, n_quantiles outside 1..32, n_critics *
+ * n_quantiles > 128, a non-finite gamma, NULL cfg / out.  PGX_E_UNSUPPORTED where a workgroup's LDS
+ *   64 * (max(K16 + 4 + 2 (H16 + 4), T4) + 16 n_critics ceil(n_quantiles / 16) + 4) bytes (16 rows)
+ * exceeds 160 KiB - 512: with one hidden layer of 16, one critic, one quantile and action_dim 3 the
+ * widest accepted obs_dim is 2471 (K16 = 2480). */
+int pgx_qc_create(const pgx_qc_config* cfg, int device, pgx_qc_handle* out);
+void pgx_qc_destroy(pgx_qc_handle h);
+/* critic.load_state_dict / critic_target.load_state_dict: copies set `which`'s parameters into the handle
+ * and packs them there, on `stream`: a captured graph sees them at its next replay.  The sources must
+ * stay valid until the stream has run the copies. */
+int pgx_qc_set_weights(pgx_qc_handle h, int32_t which, const pgx_qc_weights* w, void* stream);
+/* The handle's plain copy of set `which` (what pgx_qc_polyak updates) into w's pointers, device or host:
+ * copy operations on `stream`, then a synchronise of it.  (critic_target.state_dict().) */
+int pgx_qc_get_weights(pgx_qc_handle h, int32_t which, const pgx_qc_weights* w, void* stream);
+/* tqc.py: current_quantiles = self.critic(observations, actions) (which = PGX_QC_ONLINE), or
+ * self.critic_target(...): one launch.  PGX_E_INVALID, before any device call and naming the field, for a
+ * NULL obs / achieved_goal / desired_goal / action / out, B <= 0, a stride below its width. */
+int pgx_qc_forward(pgx_qc_handle h, int32_t which, const pgx_qc_io* io, int32_t B, void* stream);
+/* tqc.py, the no_grad block of train(): next_quantiles = self.critic_target(next_observations,
+ * next_actions); sorted_z, _ = th.sort(next_quantiles.reshape(batch_size, -1)); sorted_z_part =
+ * sorted_z[:, :n_target_quantiles]; target_quantiles = sorted_z_part - ent_coef * next_log_prob;
+ * target_quantiles = rewards + (1 - dones) * gamma * target_quantiles: one launch (see above).
+ * pgx_qc_forward's refusals, and: a NULL reward / done / next_log_prob / ent_coef, n_target outside 1..T,
+ * reward_stride / done_stride < 1. */
+int pgx_qc_target(pgx_qc_handle h, const pgx_qc_io* io, int32_t B, int32_t n_target, void* stream);
+/* tqc.py: polyak_update(self.critic.parameters(), self.critic_target.parameters(), self.tau): one launch
+ * over the plain copies, then the packing launches (see above).  PGX_E_INVALID naming tau (checked first)
+ * for tau outside [0, 1] or NaN. */
+int pgx_qc_polyak(pgx_qc_handle h, double tau, void* stream);
+/* tqc/policies.py: self.critic_target.load_state_dict(self.critic.state_dict()): one launch. */
+int pgx_qc_sync_target(pgx_qc_handle h, void* stream);
+/* The contracts above in plain C++ on host arrays (std::fmaf; every pointer of io a host pointer, strides
+ * honoured, *io->ent_coef read), with the device entries' refusals.  w: the set to use.  forward: io->out
+ * [B, n_critics, n_quantiles]; target: io->out [B, n_target] and, non-NULL, io->quantiles_out.  Never
+ * touch a device; not a stepping path. */
+int pgx_qc_forward_host(const pgx_qc_config* cfg, const pgx_qc_weights* w, const pgx_qc_io* io, int32_t B);
+int pgx_qc_target_host(const pgx_qc_config* cfg, const pgx_qc_weights* w, const pgx_qc_io* io, int32_t B,
+                       int32_t n_target);
+
 #ifdef __cplusplus
 }
 #endif

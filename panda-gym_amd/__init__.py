@@ -18,6 +18,7 @@ from .rollout import RolloutBuffer, RolloutBufferSamples
 from .actor import Actor
 from .actor_critic import ActorCritic
 from .sde_actor import SdeActor
+from .quantile_critic import QuantileCritic
 from ._native import PgxError, load as load_native
 from .model import Model, load_model
 
@@ -27,4 +28,4 @@ __all__ = ["Box", "DictSpace", "PandaEnv", "PandaVecEnv", "make", "register_envs
            "seeded_goal", "seeded_reset", "spec", "task_draws", "pcg64_record", "pcg64_records", "pcg64_from_record", "PgxError", "load_native", "Model", "load_model",
            "HerReplayBuffer", "VecNormalize", "Normalizer", "RunningMeanStd",
            "EpisodeMonitor", "VecMonitor", "evaluate", "RolloutBuffer", "RolloutBufferSamples", "Actor", "ActorCritic",
-           "SdeActor"]
+           "SdeActor", "QuantileCritic"]

@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 from .abi import PGX_E_INVALID  # noqa: F401 (re-exported for the C-ABI tests)
-from .abi import (PgxAcConfig, PgxAcIo, PgxAcWeights, PgxActorConfig, PgxActorIo, PgxActorWeights, PgxConfig, PgxMonitorConfig, PgxMonitorIo, PgxMonitorTotals, PgxNormConfig, PgxNormIo, PgxReplayBatch,
+from .abi import (PgxAcConfig, PgxAcIo, PgxAcWeights, PgxActorConfig, PgxActorIo, PgxActorWeights, PgxConfig, PgxMonitorConfig, PgxMonitorIo, PgxMonitorTotals, PgxNormConfig, PgxNormIo, PgxQcConfig, PgxQcIo, PgxQcWeights, PgxReplayBatch,
                   PgxReplayConfig, PgxReplayStep, PgxReplayViews, PgxRolloutBatch, PgxRolloutConfig, PgxRolloutIo,
                   PgxRolloutViews, PgxSdeActorConfig, PgxSdeActorIo, PgxSdeActorWeights, PgxStateView, PgxStepOut,
                   PgxTransition)
@@ -39,6 +39,8 @@ EXPORTS = [
     "pgx_sde_actor_create", "pgx_sde_actor_destroy", "pgx_sde_actor_set_weights", "pgx_sde_actor_reset_noise",
     "pgx_sde_actor_forward", "pgx_sde_actor_state", "pgx_sde_actor_set_state", "pgx_sde_actor_get_matrices",
     "pgx_sde_actor_set_matrices", "pgx_sde_actor_get_std", "pgx_sde_actor_forward_host",
+    "pgx_qc_create", "pgx_qc_destroy", "pgx_qc_set_weights", "pgx_qc_get_weights", "pgx_qc_forward", "pgx_qc_target",
+    "pgx_qc_polyak", "pgx_qc_sync_target", "pgx_qc_forward_host", "pgx_qc_target_host",
 ]
 
 
@@ -169,6 +171,18 @@ def load(path: str = None):
     lib.pgx_sde_actor_get_std.argtypes = [C.c_void_p] * 3
     lib.pgx_sde_actor_forward_host.argtypes = [C.POINTER(PgxSdeActorConfig), C.POINTER(PgxSdeActorWeights)] + \
         [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3
+    lib.pgx_qc_create.argtypes = [C.POINTER(PgxQcConfig), C.c_int, C.POINTER(C.c_void_p)]
+    lib.pgx_qc_destroy.argtypes = [C.c_void_p]
+    lib.pgx_qc_destroy.restype = None
+    lib.pgx_qc_set_weights.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PgxQcWeights), C.c_void_p]
+    lib.pgx_qc_get_weights.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PgxQcWeights), C.c_void_p]
+    lib.pgx_qc_forward.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PgxQcIo), C.c_int32, C.c_void_p]
+    lib.pgx_qc_target.argtypes = [C.c_void_p, C.POINTER(PgxQcIo), C.c_int32, C.c_int32, C.c_void_p]
+    lib.pgx_qc_polyak.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+    lib.pgx_qc_sync_target.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pgx_qc_forward_host.argtypes = [C.POINTER(PgxQcConfig), C.POINTER(PgxQcWeights), C.POINTER(PgxQcIo), C.c_int32]
+    lib.pgx_qc_target_host.argtypes = [C.POINTER(PgxQcConfig), C.POINTER(PgxQcWeights), C.POINTER(PgxQcIo), C.c_int32,
+                                       C.c_int32]
     _libs[path] = lib
     return lib
 

@@ -1,4 +1,5 @@
-"""What the device-resident policies (``Actor``, ``ActorCritic``, ``SdeActor``) share on the Python side:
+"""What the device-resident policies (``Actor``, ``ActorCritic``, ``SdeActor``, ``QuantileCritic``) share on the
+Python side:
 resolving env, dims and device, the handle's life, the observation shaping in front of a launch, the
 parameter slots behind ``state_dict`` / ``load_state_dict``, the numpy conversions in front of the host
 model, the device noise word, and the check of a venv's persistent buffers in front of a capture.

@@ -333,6 +333,33 @@ class PgxAcIo(C.Structure):
     ]
 
 
+# QuantileCritic (include/pgx.h, pgx_qc_*)
+QC_ONLINE, QC_TARGET = 0, 1
+QC_SETS = {"online": QC_ONLINE, "target": QC_TARGET}
+QC_MAX_CRITICS, QC_MAX_QUANTILES, QC_MAX_POOL = 5, 32, 128
+
+
+class PgxQcConfig(C.Structure):
+    _fields_ = [
+        ("obs_dim", C.c_int32), ("action_dim", C.c_int32), ("n_layers", C.c_int32), ("hidden", C.c_int32 * 3),
+        ("n_critics", C.c_int32), ("n_quantiles", C.c_int32), ("gamma", C.c_double),
+    ]
+
+
+class PgxQcWeights(C.Structure):
+    _fields_ = [("weight", (C.c_void_p * 4) * 5), ("bias", (C.c_void_p * 4) * 5)]
+
+
+class PgxQcIo(C.Structure):
+    _fields_ = [
+        ("obs", C.c_void_p), ("achieved_goal", C.c_void_p), ("desired_goal", C.c_void_p), ("action", C.c_void_p),
+        ("reward", C.c_void_p), ("done", C.c_void_p), ("next_log_prob", C.c_void_p), ("ent_coef", C.c_void_p),
+        ("out", C.c_void_p), ("quantiles_out", C.c_void_p),
+        ("obs_stride", C.c_int32), ("achieved_goal_stride", C.c_int32), ("desired_goal_stride", C.c_int32),
+        ("action_stride", C.c_int32), ("reward_stride", C.c_int32), ("done_stride", C.c_int32),
+    ]
+
+
 def rollout_row_fields(obs_dim: int, action_dim: int):
     """(name, offset, width) of the RolloutBuffer batch row layout of include/pgx.h, plus row_dim."""
     f, o = [], 0

@@ -12,7 +12,8 @@ of an env or a wrapper and writes the action buffer the next step reads, so ``ca
 ``forward_host``, the host model of the kernel's arithmetic, which is a test oracle and not a way to step).
 
 PPO's actor-critic lives next door (actor_critic.py), the gSDE actor (``use_sde=True``, per-env exploration
-matrices) in sde_actor.py.  Critics for SAC / TQC and optimisers are not here.
+matrices) in sde_actor.py, TQC's critics (forward, truncated TD target, Polyak step) in quantile_critic.py.
+Optimisers are not here.
 """
 from __future__ import annotations
 

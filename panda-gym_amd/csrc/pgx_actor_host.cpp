@@ -9,11 +9,16 @@
  * restatement on a CPU.  Never touches a device; the Actor does not step through it.
  * pgx_ac_forward_host and pgx_sde_actor_forward_host (below) are the same for pgx_actor_critic.hip and
  * pgx_sde_actor.hip, over the same `stage_x`, `hidden_layers` and `linear`; the three check_config share
- * `check_common`, `check_count` and `check_widths`.
+ * `check_common`, `check_count` and `check_widths`.  pgx_qc_forward_host and pgx_qc_target_host (last) are
+ * the quantile critics' (pgx_quantile_critic.hip): the same Linears, then the pooled sort by the order
+ * rule's key, the truncation and the unfused Bellman backup; the launch checks they share with the device
+ * entry points are pgx_qc_check_launch.
  */
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "../../include/pgx.h"
@@ -247,6 +252,130 @@ extern "C" int pgx_sde_actor_forward_host(const pgx_sde_actor_config* cfg, const
                 noise_out[(size_t)e * A + d] = acc;
             }
         }
+    }
+    return PGX_OK;
+}
+
+/* ---------------------------------------------------------------- QuantileCritic (include/pgx.h) */
+
+/* pgx_qc_create's checks (no device call); `what` names the entry point */
+int pgx_qc_check_config(const pgx_qc_config* c, const char* what) {
+    if (!c) return bad(what, "null config");
+    if (c->obs_dim <= 0 || c->obs_dim > 4096) return bad(what, "obs_dim must be in 1..4096");
+    if (c->action_dim < 1 || c->action_dim > PGX_ACTOR_MAX_ACTION) return bad(what, "action_dim must be in 1..7");
+    int rc = check_count(what, "n_layers", c->n_layers);
+    if (rc == PGX_OK) rc = check_widths(what, "hidden", c->n_layers, c->hidden);
+    if (rc != PGX_OK) return rc;
+    if (c->n_critics < 1 || c->n_critics > PGX_QC_MAX_CRITICS) return bad(what, "n_critics must be in 1..5");
+    if (c->n_quantiles < 1 || c->n_quantiles > PGX_QC_MAX_QUANTILES) return bad(what, "n_quantiles must be in 1..32");
+    if (c->n_critics * c->n_quantiles > PGX_QC_MAX_POOL) return bad(what, "n_critics * n_quantiles must be <= 128");
+    if (!std::isfinite(c->gamma)) return bad(what, "gamma must be finite");
+    return PGX_OK;
+}
+
+/* the checks of one launch, pgx_qc_forward's (target false) or pgx_qc_target's, device and host alike */
+int pgx_qc_check_launch(const pgx_qc_config* c, const pgx_qc_io* io, int32_t B, bool target, int32_t n_target,
+                        const char* what) {
+    if (!io) return bad(what, "null io");
+    if (!io->obs) return bad(what, "null obs");
+    if (!io->achieved_goal) return bad(what, "null achieved_goal");
+    if (!io->desired_goal) return bad(what, "null desired_goal");
+    if (!io->action) return bad(what, "null action");
+    if (!io->out) return bad(what, "null out");
+    if (B <= 0) return bad(what, "B must be > 0");
+    if (io->obs_stride < c->obs_dim) return bad(what, "obs_stride is below obs_dim");
+    if (io->achieved_goal_stride < 3) return bad(what, "achieved_goal_stride is below 3");
+    if (io->desired_goal_stride < 3) return bad(what, "desired_goal_stride is below 3");
+    if (io->action_stride < c->action_dim) return bad(what, "action_stride is below action_dim");
+    if (!target) return PGX_OK;
+    if (!io->reward) return bad(what, "null reward");
+    if (!io->done) return bad(what, "null done");
+    if (!io->next_log_prob) return bad(what, "null next_log_prob");
+    if (!io->ent_coef) return bad(what, "null ent_coef");
+    if (n_target < 1 || n_target > c->n_critics * c->n_quantiles) return bad(what, "n_target must be in 1..n_critics * n_quantiles");
+    if (io->reward_stride < 1) return bad(what, "reward_stride is below 1");
+    if (io->done_stride < 1) return bad(what, "done_stride is below 1");
+    return PGX_OK;
+}
+
+int pgx_qc_check_weights(const pgx_qc_config* c, const pgx_qc_weights* w, const char* what) {
+    if (!w) return bad(what, "null weights");
+    for (int i = 0; i < c->n_critics; i++)
+        for (int l = 0; l <= c->n_layers; l++)
+            if (!w->weight[i][l] || !w->bias[i][l]) return bad(what, "null weight or bias pointer");
+    return PGX_OK;
+}
+
+namespace {
+
+/* the order rule's key of an f32's bits */
+uint32_t qc_key(float v) {
+    uint32_t u;
+    std::memcpy(&u, &v, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+/* row b's T quantiles, [critic][quantile], of the set w */
+void qc_row(const pgx_qc_config* cfg, const pgx_qc_weights* w, const pgx_qc_io* io, size_t b, float* x, float* y,
+            float* zz, float* out) {
+    const int od = cfg->obs_dim, A = cfg->action_dim, nl = cfg->n_layers, nq = cfg->n_quantiles;
+    for (int k = 0; k < 3; k++) x[k] = io->achieved_goal[b * io->achieved_goal_stride + k];
+    for (int k = 0; k < 3; k++) x[3 + k] = io->desired_goal[b * io->desired_goal_stride + k];
+    for (int k = 0; k < od; k++) x[6 + k] = io->obs[b * io->obs_stride + k];
+    for (int k = 0; k < A; k++) x[6 + od + k] = io->action[b * io->action_stride + k];
+    for (int c = 0; c < cfg->n_critics; c++) {
+        const float* in = hidden_layers(nl, cfg->hidden, w->weight[c], w->bias[c], x, od + 6 + A, y, zz);
+        linear(w->weight[c][nl], w->bias[c][nl], in, cfg->hidden[nl - 1], nq, false, out + (size_t)c * nq);
+    }
+}
+
+/* the epilogue of the truncated target: four operations, four roundings */
+#pragma clang fp contract(off)
+float qc_backup(float z, float ent_coef, float next_log_prob, float reward, float done, float gamma) {
+    const float t1 = ent_coef * next_log_prob;
+    const float t2 = z - t1;
+    const float m = (1.0f - done) * gamma;
+    return reward + m * t2;
+}
+#pragma clang fp contract(on)
+
+}  // namespace
+
+extern "C" int pgx_qc_forward_host(const pgx_qc_config* cfg, const pgx_qc_weights* w, const pgx_qc_io* io, int32_t B) {
+    const char* what = "pgx_qc_forward_host";
+    int rc = pgx_qc_check_config(cfg, what);
+    if (rc == PGX_OK) rc = pgx_qc_check_weights(cfg, w, what);
+    if (rc == PGX_OK) rc = pgx_qc_check_launch(cfg, io, B, false, 0, what);
+    if (rc != PGX_OK) return rc;
+    const int T = cfg->n_critics * cfg->n_quantiles;
+    std::vector<float> x(cfg->obs_dim + 6 + cfg->action_dim), y(PGX_ACTOR_MAX_WIDTH), z(PGX_ACTOR_MAX_WIDTH);
+    for (int32_t b = 0; b < B; b++) qc_row(cfg, w, io, (size_t)b, x.data(), y.data(), z.data(), io->out + (size_t)b * T);
+    return PGX_OK;
+}
+
+extern "C" int pgx_qc_target_host(const pgx_qc_config* cfg, const pgx_qc_weights* w, const pgx_qc_io* io, int32_t B,
+                                  int32_t n_target) {
+    const char* what = "pgx_qc_target_host";
+    int rc = pgx_qc_check_config(cfg, what);
+    if (rc == PGX_OK) rc = pgx_qc_check_weights(cfg, w, what);
+    if (rc == PGX_OK) rc = pgx_qc_check_launch(cfg, io, B, true, n_target, what);
+    if (rc != PGX_OK) return rc;
+    const int T = cfg->n_critics * cfg->n_quantiles;
+    const float ent = *io->ent_coef, gamma = (float)cfg->gamma;
+    std::vector<float> x(cfg->obs_dim + 6 + cfg->action_dim), y(PGX_ACTOR_MAX_WIDTH), zz(PGX_ACTOR_MAX_WIDTH);
+    float q[PGX_QC_MAX_POOL];
+    int order[PGX_QC_MAX_POOL];
+    for (int32_t b = 0; b < B; b++) {
+        qc_row(cfg, w, io, (size_t)b, x.data(), y.data(), zz.data(), q);
+        if (io->quantiles_out)
+            for (int i = 0; i < T; i++) io->quantiles_out[(size_t)b * T + i] = q[i];
+        for (int i = 0; i < T; i++) order[i] = i;
+        /* stable: equal keys keep their flat-index order */
+        std::stable_sort(order, order + T, [&q](int i, int j) { return qc_key(q[i]) < qc_key(q[j]); });
+        for (int k = 0; k < n_target; k++)
+            io->out[(size_t)b * n_target + k] =
+                qc_backup(q[order[k]], ent, io->next_log_prob[b], io->reward[(size_t)b * io->reward_stride],
+                          io->done[(size_t)b * io->done_stride], gamma);
     }
     return PGX_OK;
 }

@@ -1,6 +1,6 @@
 /*
- * pgx_mlp.h -- the device side the policy units (pgx_actor.hip, pgx_actor_critic.hip, pgx_sde_actor.hip)
- * share: the plan of one stack of Linears, the feature staging their forward kernels open with, one
+ * pgx_mlp.h -- the device side the policy units (pgx_actor.hip, pgx_actor_critic.hip, pgx_sde_actor.hip,
+ * pgx_quantile_critic.hip) share: the plan of one stack of Linears, the feature staging their forward kernels open with, one
  * Linear over a workgroup's env tile as v_mfma_f32_16x16x4_f32 on activations kept in LDS, the loop that
  * runs a stack through two LDS regions, the Gaussian draw from the Philox stream, the advance of a
  * device-resident noise word, and the kernel that packs torch-layout weights for the Linear.  Arithmetic
@@ -25,7 +25,7 @@ constexpr int MAX_LINEAR = PGX_ACTOR_MAX_LAYERS + 1;   /* the hidden layers and 
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-/* one stack of Linears: the hidden layers, then a head of one tile */
+/* one stack of Linears: the hidden layers, then a head of one tile (two for 17..32 quantiles) */
 struct MlpPlan {
     int32_t n_linear;
     int32_t nkb[MAX_LINEAR], ntiles[MAX_LINEAR];   /* 16-wide k blocks and output tiles per Linear */

@@ -1,6 +1,6 @@
 /*
- * pgx_policy.h -- the host side the policy units (pgx_actor.hip, pgx_actor_critic.hip, pgx_sde_actor.hip)
- * share: planning a stack of Linears, the tile choice, the handle's one device allocation, copy-and-pack
+ * pgx_policy.h -- the host side the policy units (pgx_actor.hip, pgx_actor_critic.hip, pgx_sde_actor.hip,
+ * pgx_quantile_critic.hip) share: planning a stack of Linears, the tile choice, the handle's one device allocation, copy-and-pack
  * of a Linear, the noise word's read and write, the launch of a forward kernel in its tile size.  The
  * device side: pgx_mlp.h.  Everything here has internal linkage: each unit compiles its own copy.
  */
@@ -45,7 +45,7 @@ int plan_stack(MlpPlan* p, int in_dim, const int32_t* hidden, int nl, int head_o
         int o, in;
         linear_dims(in_dim, hidden, nl, head_out, l, &o, &in);
         p->nkb[l] = (in + 15) / 16;
-        p->ntiles[l] = l < nl ? (o + 15) / 16 : 1;
+        p->ntiles[l] = (o + 15) / 16;   /* the head: one tile up to 16 outputs, two for the quantile critics' 17..32 */
         p->woff[l] = (int32_t)*off;
         *off += (size_t)p->nkb[l] * p->ntiles[l] * 256;
         p->boff[l] = (int32_t)*off;
@@ -59,12 +59,13 @@ int plan_stack(MlpPlan* p, int in_dim, const int32_t* hidden, int nl, int head_o
     return widest;
 }
 
-/* Env tiles of 16 per workgroup: 2 from 4096 envs on (each workgroup streams every weight once, and at
- * 4096 x [256, 256] the halved L2 traffic outweighs the halved workgroup count: DESIGN.md) or as env_var
- * (NULL: none) says, 16 or 32 envs; 1 where lds_bytes(2) does not fit; 0 where lds_bytes(1) does not */
+/* Env tiles of 16 per workgroup: 2 from two_from envs on (4096: each workgroup streams every weight once,
+ * and at 4096 x [256, 256] the halved L2 traffic outweighs the halved workgroup count: DESIGN.md; the
+ * quantile critics measured 2 ahead from 17 rows on) or as env_var (NULL: none) says, 16 or 32 envs; 1
+ * where lds_bytes(2) does not fit; 0 where lds_bytes(1) does not */
 template <class F>
-int choose_tile(int n_envs, const char* env_var, F lds_bytes) {
-    int mt = n_envs >= 4096 ? 2 : 1;
+int choose_tile(int n_envs, const char* env_var, F lds_bytes, int two_from = 4096) {
+    int mt = n_envs >= two_from ? 2 : 1;
     if (env_var)
         if (const char* t = std::getenv(env_var)) mt = std::atoi(t) == 32 ? 2 : 1;
     if (lds_bytes(mt) > LDS_LIMIT) mt = 1;

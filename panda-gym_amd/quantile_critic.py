@@ -1,0 +1,310 @@
+"""Device-resident quantile critics: sb3_contrib TQC's ``critic`` / ``critic_target`` forward and the
+truncated TD target of ``TQC.train`` as one HIP launch.
+
+The reference trains TQC with HER (hyperparameters.py: batch 256, ``gradient_steps`` 8, ``net_arch`` [256,
+256] or [400, 300], ``top_quantiles_to_drop_per_net`` 5 in ``TQC_v2``).  Every no-grad line of a gradient
+step -- ``critic_target(next_obs, next_actions)``, the pooled sort, the truncation, the entropy term, the
+Bellman backup, the Polyak step -- is inference on ``Linear + ReLU`` stacks, and ``QuantileCritic`` runs it
+in libpgx.so (pgx_quantile_critic.hip; C-ABI, arithmetic contract and the sort's order rule in
+include/pgx.h, section "QuantileCritic").  A launch reads dense tensors or, through row strides, the fields
+of a HER batch's ``rows`` (``buf.alloc_batch`` / ``buf.sample_into``) where they lie.  (Through the C entry
+point, ``n_quantiles = 1`` with ``n_target = 1`` is SAC's / TD3's ``min`` over the critics.)  No CPU
+fallback: with ``device="cpu"`` a ``QuantileCritic`` only holds and maps parameters (``load_state_dict`` /
+``state_dict`` / ``forward_host`` / ``td_target_host``, the host models of the kernels' arithmetic, which
+are test oracles).
+
+Not here: gradients, the quantile Huber loss, the actor loss's Q mean, an action log-probability from the
+device actors (``next_actions`` and ``next_log_prob`` are the caller's buffers), optimisers.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import abi
+from ._policy import Policy, torch
+
+SETS = ("online", "target")
+SD_PREFIX = {"online": "critic.", "target": "critic_target."}
+
+
+class QuantileCritic(Policy):
+    """sb3_contrib's TQC critics (``tqc/policies.py`` ``Critic``) and their target copy on the device.
+
+    ``env``: a ``PandaVecEnv`` or a wrapper of one (the dims and the device are read from it), or pass
+    ``obs_dim`` and ``action_dim``.  ``net_arch``: 1 to 3 hidden widths of 1 to 512.  ``n_critics`` 1..5,
+    ``n_quantiles`` 1..32, their product at most 128.  The target keeps the ``n_target = n_critics *
+    (n_quantiles - top_quantiles_to_drop_per_net)`` lowest of the pooled quantiles.  The batch size is
+    whatever a call is given.  Both parameter sets are zero until ``load_state_dict``."""
+
+    _PREFIX = "pgx_qc"
+    _WHO = "critic"
+
+    def __init__(self, env: Any = None, obs_dim: Optional[int] = None, action_dim: Optional[int] = None,
+                 net_arch: Sequence[int] = (256, 256), n_critics: int = 2, n_quantiles: int = 25,
+                 top_quantiles_to_drop_per_net: int = 2, gamma: float = 0.99, device: Any = None):
+        self._need_torch()
+        self._resolve(env, obs_dim, action_dim, 1, device)   # (no per-env storage: the batch is a launch argument)
+        self.net_arch = tuple(int(w) for w in net_arch)
+        self.n_critics, self.n_quantiles = int(n_critics), int(n_quantiles)
+        self.top_quantiles_to_drop_per_net, self.gamma = int(top_quantiles_to_drop_per_net), float(gamma)
+        self.n_pool = self.n_critics * self.n_quantiles
+        self.n_target = self.n_pool - self.top_quantiles_to_drop_per_net * self.n_critics
+        if self.top_quantiles_to_drop_per_net < 0 or (self.n_pool > 0 and self.n_target < 1):
+            raise ValueError(f"top_quantiles_to_drop_per_net must be in 0..n_quantiles - 1, got "
+                             f"{top_quantiles_to_drop_per_net}")
+        cfg = abi.PgxQcConfig()
+        cfg.obs_dim, cfg.action_dim, cfg.n_layers = self.obs_dim, self.action_dim, len(self.net_arch)
+        for i, w in enumerate(self.net_arch[:abi.ACTOR_MAX_LAYERS]):
+            cfg.hidden[i] = w
+        cfg.n_critics, cfg.n_quantiles, cfg.gamma = self.n_critics, self.n_quantiles, self.gamma
+        self._cfg = cfg
+        # the parameters as given (torch layout), per set and critic: what set_weights reads
+        dims = [self.obs_dim + 6 + self.action_dim] + list(self.net_arch) + [self.n_quantiles]
+        nc = min(max(self.n_critics, 0), abi.QC_MAX_CRITICS)   # (out of range: the library rejects it below)
+        shapes = [(max(dims[i + 1], 0), dims[i]) for i in range(min(len(dims) - 1, 4))]
+        self._names = [f"qf{c}.{2 * l}" for c in range(nc) for l in range(len(shapes))]
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.device)  # noqa: E731
+        self._ws = {s: [z(*shp) for _ in range(nc) for shp in shapes] for s in SETS}
+        self._bs = {s: [z(shp[0]) for _ in range(nc) for shp in shapes] for s in SETS}
+        self._n_linear = len(shapes)
+        self._loading: Tuple[str, ...] = SETS
+        self._stale = False   # the target tensors here lag the handle's copy (after a Polyak step or a sync)
+        self._open()
+
+    # ------------------------------------------------------------ plumbing
+    def _open(self) -> None:
+        """The device handle with both sets pushed; on a CPU device the library's argument checks either
+        way: the host model on one zero row."""
+        if self.device.type == "cuda":
+            super()._open()
+        else:
+            self.forward_host({"observation": np.zeros((1, self.obs_dim), np.float32),
+                               "achieved_goal": np.zeros((1, 3), np.float32), "desired_goal": np.zeros((1, 3), np.float32)},
+                              np.zeros((1, self.action_dim), np.float32))
+
+    @staticmethod
+    def _which(which: str) -> str:
+        if which not in SETS:
+            raise ValueError(f"which must be one of {list(SETS)}, got {which!r}")
+        return which
+
+    def _weights_struct(self, ws, bs) -> abi.PgxQcWeights:
+        w = abi.PgxQcWeights()
+        for i, (x, y) in enumerate(zip(ws, bs)):
+            c, l = divmod(i, self._n_linear)
+            w.weight[c][l], w.bias[c][l] = x, y
+        return w
+
+    def _set_struct(self, which: str) -> abi.PgxQcWeights:
+        return self._weights_struct([t.data_ptr() for t in self._ws[which]], [t.data_ptr() for t in self._bs[which]])
+
+    def _push(self) -> None:
+        for s in self._loading:
+            w = self._set_struct(s)
+            self._lib_call("set_weights", self._h, abi.QC_SETS[s], C.byref(w), self._stream())
+
+    def _pull_target(self) -> None:
+        """The handle's plain copy of the target set into the tensors here (after a Polyak step or a sync)."""
+        if self._h is not None and self._stale:
+            w = self._set_struct("target")
+            self._lib_call("get_weights", self._h, abi.QC_TARGET, C.byref(w), self._stream())
+            self._stale = False
+
+    # ----------------------------------------------------------- parameters
+    def _set_pairs(self, which: str, prefix: str = "") -> List[Tuple[str, "torch.Tensor"]]:
+        out = []
+        for name, w, b in zip(self._names, self._ws[which], self._bs[which]):
+            out += [(f"{prefix}{name}.weight", w), (f"{prefix}{name}.bias", b)]
+        return out
+
+    def _slots(self) -> List[Tuple[str, "torch.Tensor"]]:
+        """The sets a load is filling, under a whole policy's key names."""
+        return [p for s in self._loading for p in self._set_pairs(s, SD_PREFIX[s])]
+
+    def state_dict(self, which: str = "online") -> Dict[str, "torch.Tensor"]:
+        """Set ``which``'s parameters (``"online"``: ``critic``; ``"target"``: ``critic_target``, as the last
+        Polyak step left it) under sb3_contrib's key names ``qf{i}.{0,2,4}.weight|bias`` (copies); ``"both"``:
+        the two under a policy's ``critic.`` / ``critic_target.`` prefixes."""
+        self._pull_target()
+        if which == "both":
+            return {k: t.clone() for s in SETS for k, t in self._set_pairs(s, SD_PREFIX[s])}
+        return {k: t.clone() for k, t in self._set_pairs(self._which(which))}
+
+    def load_state_dict(self, sd: Dict[str, Any], which: Optional[str] = None) -> None:
+        """Load critic parameters.  A whole policy's state dict (``critic.qf0.0.weight`` ...,
+        ``critic_target.qf0.0.weight`` ...; everything else ignored) fills every set whose prefix it holds, or
+        with ``which`` that set alone; a critic's own dict (``qf0.0.weight`` ...) fills set ``which``, the
+        online one by default.  Every key is validated before the first parameter is copied.  The packed
+        weights in the handle are replaced on the current stream: a captured graph uses them at its next
+        replay."""
+        prefixed = any(k.startswith(p) for k in sd for p in SD_PREFIX.values())
+        if which is not None:
+            sets: Tuple[str, ...] = (self._which(which),)
+        elif prefixed:
+            sets = tuple(s for s in SETS if any(k.startswith(SD_PREFIX[s]) for k in sd))
+        else:
+            sets = ("online",)
+        if not prefixed:
+            sd = {f"{SD_PREFIX[s]}{k}": v for s in sets for k, v in sd.items()}
+        if "target" not in sets:
+            self._pull_target()   # (a later state_dict must not read a stale target over this load)
+        self._loading = sets
+        try:
+            self._load_slots(sd)
+            if "target" in sets:
+                self._stale = False
+        finally:
+            self._loading = SETS
+
+    # --------------------------------------------------------------- launches
+    def _field(self, x, width: int, B: Optional[int], name: str):
+        """A row-indexed input as (tensor, row stride in floats): a device f32 tensor [B, width] (or [B] for
+        width 1) whose rows are contiguous is read in place, whatever its row stride; anything else is
+        copied to a dense one."""
+        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+        if t.dim() == 1 and width == 1:
+            t = t.unsqueeze(1)
+        if t.dim() != 2 or t.shape[1] != width or (B is not None and t.shape[0] != B):
+            raise ValueError(f"{name}: expected shape [{'B' if B is None else B}, {width}], got {list(t.shape)}")
+        ok = t.dtype == torch.float32 and t.device == self.device and (width == 1 or t.stride(1) == 1) \
+            and (t.shape[0] == 1 or t.stride(0) >= width)
+        if not ok:
+            t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        return t, (width if t.shape[0] == 1 else int(t.stride(0)))
+
+    def _io(self, obs: Dict[str, Any], actions, B: Optional[int] = None):
+        o, so = self._field(obs["observation"], self.obs_dim, B, "observation")
+        B = int(o.shape[0])
+        ag, sag = self._field(obs["achieved_goal"], 3, B, "achieved_goal")
+        dg, sdg = self._field(obs["desired_goal"], 3, B, "desired_goal")
+        a, sa = self._field(actions, self.action_dim, B, "actions")
+        io = abi.PgxQcIo()
+        io.obs, io.achieved_goal, io.desired_goal, io.action = o.data_ptr(), ag.data_ptr(), dg.data_ptr(), a.data_ptr()
+        io.obs_stride, io.achieved_goal_stride, io.desired_goal_stride, io.action_stride = so, sag, sdg, sa
+        return io, B, [o, ag, dg, a]
+
+    def _out(self, out, B: int, width: int) -> "torch.Tensor":
+        if out is None:
+            return torch.empty((B, width), dtype=torch.float32, device=self.device)
+        if not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != self.device \
+                or not out.is_contiguous() or out.dim() != 2 or out.shape[0] < B or out.shape[1] != width:
+            raise ValueError(f"out must be a contiguous f32 [>= {B}, {width}] tensor on {self.device}")
+        return out
+
+    def critic(self, obs: Dict[str, Any], actions, target: bool = False, out=None) -> "torch.Tensor":
+        """Quantiles [B, n_critics, n_quantiles] of ``critic(obs, actions)`` (``target``: of
+        ``critic_target``): one launch.  ``obs``: the observation dict, [B, .] each; device f32 tensors, views
+        into a HER batch's rows included, are read in place.  ``out``: a contiguous f32 [>= B, n_critics *
+        n_quantiles] tensor to fill (returned as it is; its rows past B are left alone)."""
+        self._need_device()
+        io, B, keep = self._io(obs, actions)
+        q = self._out(out, B, self.n_pool)
+        io.out = q.data_ptr()
+        self._lib_call("forward", self._h, abi.QC_TARGET if target else abi.QC_ONLINE, C.byref(io), B, self._stream())
+        self._keep = keep + [q]
+        return q.view(B, self.n_critics, self.n_quantiles) if out is None else out
+
+    def td_target(self, next_obs: Dict[str, Any], next_actions, next_log_prob, rewards, dones, ent_coef, out=None,
+                  quantiles=None) -> "torch.Tensor":
+        """``TQC.train``'s target quantiles [B, n_target]: ``critic_target(next_obs, next_actions)``, pooled,
+        sorted, the lowest ``n_target`` kept, ``- ent_coef * next_log_prob``, ``rewards + (1 - dones) * gamma
+        *``: one launch.  ``rewards`` / ``dones``: [B] or [B, 1] f32; ``ent_coef``: a device tensor of one
+        float, read at every launch (a replayed graph sees its current value), or a number.  ``out``: a
+        contiguous f32 [>= B, n_target] tensor to fill (its rows past B are left alone).  ``quantiles``
+        (debug): a contiguous f32 [B, n_critics * n_quantiles] tensor that receives the unsorted pool."""
+        self._need_device()
+        io, B, keep = self._io(next_obs, next_actions)
+        r, io.reward_stride = self._field(rewards, 1, B, "rewards")
+        d, io.done_stride = self._field(dones, 1, B, "dones")
+        lp, _ = self._field(next_log_prob, 1, B, "next_log_prob")
+        if not lp.is_contiguous():
+            lp = lp.contiguous()
+        e = ent_coef if torch.is_tensor(ent_coef) else torch.as_tensor(float(ent_coef))
+        if e.numel() != 1:
+            raise ValueError("ent_coef must hold one float")
+        e = e.detach().to(device=self.device, dtype=torch.float32).reshape(1)
+        t = self._out(out, B, self.n_target)
+        io.reward, io.done, io.next_log_prob, io.ent_coef, io.out = r.data_ptr(), d.data_ptr(), lp.data_ptr(), \
+            e.data_ptr(), t.data_ptr()
+        if quantiles is not None:
+            io.quantiles_out = self._out(quantiles, B, self.n_pool).data_ptr()
+        self._lib_call("target", self._h, C.byref(io), B, self.n_target, self._stream())
+        self._keep = keep + [r, d, lp, e, t, quantiles]
+        return t
+
+    def td_target_rows(self, batch: Dict[str, "torch.Tensor"], next_actions, next_log_prob, ent_coef,
+                       out=None) -> "torch.Tensor":
+        """``td_target`` on a HER batch (``buf.alloc_batch`` / ``buf.sample_into``): ``next_obs``,
+        ``next_achieved_goal``, ``next_desired_goal``, ``reward`` and ``done`` are read from ``batch["rows"]``
+        in place."""
+        nxt = {"observation": batch["next_obs"], "achieved_goal": batch["next_achieved_goal"],
+               "desired_goal": batch["next_desired_goal"]}
+        return self.td_target(nxt, next_actions, next_log_prob, batch["reward"], batch["done"], ent_coef, out=out)
+
+    def polyak_update(self, tau: float) -> None:
+        """SB3's ``polyak_update(critic.parameters(), critic_target.parameters(), tau)`` on the handle's
+        copies, by the rule of include/pgx.h (``t = fmaf(tau, p, t * (1 - tau))``), then the target's
+        packing, on the current stream: the next target launch, eager or a replay, uses it.  Device only."""
+        self._need_device()
+        self._lib_call("polyak", self._h, C.c_double(float(tau)), self._stream())
+        self._stale = True
+
+    def sync_target(self) -> None:
+        """``critic_target.load_state_dict(critic.state_dict())``: the online set into the target, bit for
+        bit, one launch on the current stream.  Device only."""
+        self._need_device()
+        self._lib_call("sync_target", self._h, self._stream())
+        self._stale = True
+
+    # ------------------------------------------------------------ host models
+    def _host_io(self, obs: Dict[str, Any], actions):
+        o, n = self._host_obs(obs)
+        a = np.ascontiguousarray(actions.cpu().numpy() if torch.is_tensor(actions) else actions, dtype=np.float32)
+        if o["observation"].shape != (n, self.obs_dim) or a.shape != (n, self.action_dim):
+            raise ValueError(f"expected observation [n, {self.obs_dim}] and actions [n, {self.action_dim}]")
+        io = abi.PgxQcIo()
+        io.obs, io.achieved_goal, io.desired_goal, io.action = (abi.ptr(o["observation"]), abi.ptr(o["achieved_goal"]),
+                                                                abi.ptr(o["desired_goal"]), abi.ptr(a))
+        io.obs_stride, io.achieved_goal_stride, io.desired_goal_stride, io.action_stride = self.obs_dim, 3, 3, \
+            self.action_dim
+        return io, n, [o, a]
+
+    def _host_set(self, which: str):
+        if which == "target":
+            self._pull_target()
+        ws = [np.ascontiguousarray(t.cpu().numpy()) for t in self._ws[which]]
+        bs = [np.ascontiguousarray(t.cpu().numpy()) for t in self._bs[which]]
+        return self._weights_struct([x.ctypes.data for x in ws], [x.ctypes.data for x in bs]), [ws, bs]
+
+    def forward_host(self, obs: Dict[str, Any], actions, target: bool = False) -> np.ndarray:
+        """Quantiles [n, n_critics, n_quantiles] numpy f32 from the library's host model of the kernel's
+        arithmetic.  A test oracle."""
+        io, n, keep = self._host_io(obs, actions)
+        w, keep_w = self._host_set("target" if target else "online")
+        out = np.zeros((n, self.n_critics, self.n_quantiles), np.float32)
+        io.out = abi.ptr(out)
+        self._lib_call("forward_host", C.byref(self._cfg), C.byref(w), C.byref(io), n)
+        return out
+
+    def td_target_host(self, next_obs: Dict[str, Any], next_actions, next_log_prob, rewards, dones, ent_coef,
+                       n_target: Optional[int] = None, return_quantiles: bool = False):
+        """``td_target`` [n, n_target] numpy f32 from the library's host model (the target set as the last
+        Polyak step left it).  ``return_quantiles``: also the unsorted pool [n, n_critics * n_quantiles]."""
+        io, n, keep = self._host_io(next_obs, next_actions)
+        w, keep_w = self._host_set("target")
+        f = lambda x: np.ascontiguousarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x,  # noqa: E731
+                                           dtype=np.float32).reshape(-1)
+        r, d, lp, e = f(rewards), f(dones), f(next_log_prob), f(ent_coef)
+        if r.shape != (n,) or d.shape != (n,) or lp.shape != (n,) or e.shape != (1,):
+            raise ValueError("rewards, dones and next_log_prob must hold n floats, ent_coef one")
+        nt = self.n_target if n_target is None else int(n_target)
+        out = np.zeros((n, max(nt, 0)), np.float32)
+        pool = np.zeros((n, self.n_pool), np.float32)
+        io.reward, io.done, io.next_log_prob, io.ent_coef = abi.ptr(r), abi.ptr(d), abi.ptr(lp), abi.ptr(e)
+        io.reward_stride = io.done_stride = 1
+        io.out, io.quantiles_out = abi.ptr(out), abi.ptr(pool)
+        self._lib_call("target_host", C.byref(self._cfg), C.byref(w), C.byref(io), n, nt)
+        return (out, pool) if return_quantiles else out
