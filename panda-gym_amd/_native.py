@@ -7,41 +7,138 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import Any, Dict, Tuple
 
+from . import abi
 from .abi import PGX_E_INVALID  # noqa: F401 (re-exported for the C-ABI tests)
-from .abi import (PgxAcConfig, PgxAcIo, PgxAcWeights, PgxActorConfig, PgxActorIo, PgxActorWeights, PgxConfig, PgxMonitorConfig, PgxMonitorIo, PgxMonitorTotals, PgxNormConfig, PgxNormIo, PgxQcConfig, PgxQcIo, PgxQcWeights, PgxReplayBatch,
-                  PgxReplayConfig, PgxReplayStep, PgxReplayViews, PgxRolloutBatch, PgxRolloutConfig, PgxRolloutIo,
-                  PgxRolloutViews, PgxSdeActorConfig, PgxSdeActorIo, PgxSdeActorWeights, PgxStateView, PgxStepOut,
-                  PgxTransition)
 
 LIB_PATH = os.environ.get("PGX_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpgx.so")
 
-EXPORTS = [
-    "pgx_version", "pgx_last_error", "pgx_obs_dim", "pgx_action_dim", "pgx_dev_model_bytes", "pgx_create", "pgx_destroy",
-    "pgx_get_state", "pgx_reset", "pgx_step", "pgx_step_kernel", "pgx_sample_actions", "pgx_compute_reward",
-    "pgx_state_bytes", "pgx_save_state", "pgx_restore_state", "pgx_snapshot", "pgx_restore", "pgx_release",
-    "pgx_set_rng_streams", "pgx_get_rng_streams",
-    "pgx_replay_create", "pgx_replay_destroy", "pgx_replay_add", "pgx_replay_size", "pgx_replay_sample",
-    "pgx_replay_episode_arrays", "pgx_replay_row_dim", "pgx_replay_row_stride",
-    "pgx_replay_set_last", "pgx_replay_collect", "pgx_replay_truncate_last_trajectory", "pgx_replay_state",
-    "pgx_replay_arrays",
-    "pgx_norm_create", "pgx_norm_destroy", "pgx_norm_step", "pgx_norm_reset", "pgx_norm_rows", "pgx_norm_apply",
-    "pgx_norm_set_training", "pgx_norm_set_keys", "pgx_norm_get_stats", "pgx_norm_set_stats",
-    "pgx_monitor_create", "pgx_monitor_destroy", "pgx_monitor_step", "pgx_monitor_reset", "pgx_monitor_clear",
-    "pgx_monitor_set_targets", "pgx_monitor_get_totals", "pgx_monitor_read", "pgx_monitor_get_env_state",
-    "pgx_rollout_row_dim", "pgx_rollout_row_stride", "pgx_rollout_create", "pgx_rollout_destroy", "pgx_rollout_add",
-    "pgx_rollout_compute_returns_and_advantage", "pgx_rollout_permutation", "pgx_rollout_gather", "pgx_rollout_reset",
-    "pgx_rollout_set_last", "pgx_rollout_state", "pgx_rollout_arrays",
-    "pgx_actor_create", "pgx_actor_destroy", "pgx_actor_set_weights", "pgx_actor_forward", "pgx_actor_state",
-    "pgx_actor_set_state", "pgx_actor_forward_host",
-    "pgx_ac_create", "pgx_ac_destroy", "pgx_ac_set_weights", "pgx_ac_forward", "pgx_ac_values", "pgx_ac_state",
-    "pgx_ac_set_state", "pgx_ac_forward_host",
-    "pgx_sde_actor_create", "pgx_sde_actor_destroy", "pgx_sde_actor_set_weights", "pgx_sde_actor_reset_noise",
-    "pgx_sde_actor_forward", "pgx_sde_actor_state", "pgx_sde_actor_set_state", "pgx_sde_actor_get_matrices",
-    "pgx_sde_actor_set_matrices", "pgx_sde_actor_get_std", "pgx_sde_actor_forward_host",
-    "pgx_qc_create", "pgx_qc_destroy", "pgx_qc_set_weights", "pgx_qc_get_weights", "pgx_qc_forward", "pgx_qc_target",
-    "pgx_qc_polyak", "pgx_qc_sync_target", "pgx_qc_forward_host", "pgx_qc_target_host",
-]
+INT = "int"   # a restype to leave alone: ctypes' default, C int
+P, I32, I64, U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
+ptr = C.POINTER
+
+
+def _int(*argtypes) -> Tuple[list, Any]:
+    return list(argtypes), INT
+
+
+# Every entry point of include/pgx.h: name -> (argtypes, restype), by unit.
+SIGNATURES: Dict[str, Tuple[list, Any]] = {
+    "pgx_version": ([], C.c_char_p),
+    "pgx_last_error": ([], C.c_char_p),
+    "pgx_obs_dim": _int(ptr(abi.PgxConfig)),
+    "pgx_action_dim": _int(ptr(abi.PgxConfig)),
+    "pgx_dev_model_bytes": _int(ptr(abi.PgxConfig), P, I64),
+    "pgx_create": _int(ptr(abi.PgxConfig), C.c_int, ptr(P)),
+    "pgx_destroy": ([P], None),
+    "pgx_get_state": _int(P, ptr(abi.PgxStateView)),
+    "pgx_reset": _int(P, P, P, P, ptr(abi.PgxStepOut), P),
+    "pgx_step": _int(P, P, ptr(abi.PgxStepOut), P),
+    "pgx_step_kernel": ([P], C.c_char_p),
+    "pgx_sample_actions": _int(P, P, U64, P),
+    "pgx_compute_reward": _int(P, P, I64, I32, C.c_double, P, P),
+    "pgx_state_bytes": _int(P, ptr(I64)),
+    "pgx_save_state": _int(P, P, P),
+    "pgx_restore_state": _int(P, P, P),
+    "pgx_snapshot": _int(P, ptr(I32), P),
+    "pgx_restore": _int(P, I32, P),
+    "pgx_release": _int(P, I32),
+    "pgx_set_rng_streams": _int(P, P, P),
+    "pgx_get_rng_streams": _int(P, P, P),
+
+    "pgx_replay_create": _int(ptr(abi.PgxReplayConfig), C.c_int, ptr(P)),
+    "pgx_replay_destroy": ([P], None),
+    "pgx_replay_add": _int(P, ptr(abi.PgxTransition), P),
+    "pgx_replay_size": ([P], I64),
+    "pgx_replay_sample": _int(P, I64, U64, ptr(abi.PgxReplayBatch), P),
+    "pgx_replay_episode_arrays": _int(P, ptr(P), ptr(P), ptr(P)),
+    "pgx_replay_row_dim": _int(ptr(abi.PgxReplayConfig)),
+    "pgx_replay_row_stride": _int(ptr(abi.PgxReplayConfig)),
+    "pgx_replay_set_last": _int(*[P] * 5),
+    "pgx_replay_collect": _int(P, ptr(abi.PgxReplayStep), P),
+    "pgx_replay_truncate_last_trajectory": _int(P, I32, P),
+    "pgx_replay_state": _int(P, ptr(I64), ptr(I32), ptr(C.c_uint32), I32, P),
+    "pgx_replay_arrays": _int(P, ptr(abi.PgxReplayViews)),
+
+    "pgx_norm_create": _int(ptr(abi.PgxNormConfig), C.c_int, ptr(P)),
+    "pgx_norm_destroy": ([P], None),
+    "pgx_norm_step": _int(P, ptr(abi.PgxNormIo), P),
+    "pgx_norm_reset": _int(P, ptr(abi.PgxNormIo), P),
+    "pgx_norm_rows": _int(P, P, I64, I32, I32, P),
+    "pgx_norm_apply": _int(P, I32, I32, P, P, I64, P),
+    "pgx_norm_set_training": _int(P, I32, P),
+    "pgx_norm_set_keys": _int(P, I32, I32),
+    "pgx_norm_get_stats": _int(*[P] * 6),
+    "pgx_norm_set_stats": _int(*[P] * 6),
+
+    "pgx_monitor_create": _int(ptr(abi.PgxMonitorConfig), C.c_int, ptr(P)),
+    "pgx_monitor_destroy": ([P], None),
+    "pgx_monitor_step": _int(P, ptr(abi.PgxMonitorIo), P),
+    "pgx_monitor_reset": _int(P, P, P),
+    "pgx_monitor_clear": _int(P, P),
+    "pgx_monitor_set_targets": _int(P, P, P),
+    "pgx_monitor_get_totals": _int(P, ptr(abi.PgxMonitorTotals), P),
+    "pgx_monitor_read": _int(P, I32, *[P] * 6, ptr(I32), P),
+    "pgx_monitor_get_env_state": _int(*[P] * 6),
+
+    "pgx_rollout_row_dim": _int(ptr(abi.PgxRolloutConfig)),
+    "pgx_rollout_row_stride": _int(ptr(abi.PgxRolloutConfig)),
+    "pgx_rollout_create": _int(ptr(abi.PgxRolloutConfig), C.c_int, ptr(P)),
+    "pgx_rollout_destroy": ([P], None),
+    "pgx_rollout_add": _int(P, ptr(abi.PgxRolloutIo), P),
+    "pgx_rollout_compute_returns_and_advantage": _int(P, P, P, P),
+    "pgx_rollout_permutation": _int(P, U64, P, P),
+    "pgx_rollout_gather": _int(P, P, I64, ptr(abi.PgxRolloutBatch), P),
+    "pgx_rollout_reset": _int(P, P),
+    "pgx_rollout_set_last": _int(*[P] * 6),
+    "pgx_rollout_state": _int(P, ptr(I32), ptr(C.c_uint32), I32, P),
+    "pgx_rollout_arrays": _int(P, ptr(abi.PgxRolloutViews)),
+
+    "pgx_actor_create": _int(ptr(abi.PgxActorConfig), C.c_int, ptr(P)),
+    "pgx_actor_destroy": ([P], None),
+    "pgx_actor_set_weights": _int(P, ptr(abi.PgxActorWeights), P),
+    "pgx_actor_forward": _int(P, ptr(abi.PgxActorIo), I32, P),
+    "pgx_actor_state": _int(P, ptr(U64), P),
+    "pgx_actor_set_state": _int(P, U64, P),
+    "pgx_actor_forward_host": _int(ptr(abi.PgxActorConfig), ptr(abi.PgxActorWeights), P, P, P, I32, P, P),
+
+    "pgx_ac_create": _int(ptr(abi.PgxAcConfig), C.c_int, ptr(P)),
+    "pgx_ac_destroy": ([P], None),
+    "pgx_ac_set_weights": _int(P, ptr(abi.PgxAcWeights), P),
+    "pgx_ac_forward": _int(P, ptr(abi.PgxAcIo), I32, P),
+    "pgx_ac_values": _int(*[P] * 7),
+    "pgx_ac_state": _int(P, ptr(U64), P),
+    "pgx_ac_set_state": _int(P, U64, P),
+    "pgx_ac_forward_host": _int(ptr(abi.PgxAcConfig), ptr(abi.PgxAcWeights), P, P, P, I32, P, P),
+
+    "pgx_sde_actor_create": _int(ptr(abi.PgxSdeActorConfig), C.c_int, ptr(P)),
+    "pgx_sde_actor_destroy": ([P], None),
+    "pgx_sde_actor_set_weights": _int(P, ptr(abi.PgxSdeActorWeights), P),
+    "pgx_sde_actor_reset_noise": _int(*[P] * 4),
+    "pgx_sde_actor_forward": _int(P, ptr(abi.PgxSdeActorIo), I32, P),
+    "pgx_sde_actor_state": _int(P, ptr(U64), P),
+    "pgx_sde_actor_set_state": _int(P, U64, P),
+    "pgx_sde_actor_get_matrices": _int(P, P, P),
+    "pgx_sde_actor_set_matrices": _int(P, P, P),
+    "pgx_sde_actor_get_std": _int(P, P, P),
+    "pgx_sde_actor_forward_host": _int(ptr(abi.PgxSdeActorConfig), ptr(abi.PgxSdeActorWeights), P, P, P, P, I32,
+                                       P, P, P),
+
+    "pgx_qc_create": _int(ptr(abi.PgxQcConfig), C.c_int, ptr(P)),
+    "pgx_qc_destroy": ([P], None),
+    "pgx_qc_set_weights": _int(P, I32, ptr(abi.PgxQcWeights), P),
+    "pgx_qc_get_weights": _int(P, I32, ptr(abi.PgxQcWeights), P),
+    "pgx_qc_forward": _int(P, I32, ptr(abi.PgxQcIo), I32, P),
+    "pgx_qc_target": _int(P, ptr(abi.PgxQcIo), I32, I32, P),
+    "pgx_qc_polyak": _int(P, C.c_double, P),
+    "pgx_qc_sync_target": _int(P, P),
+    "pgx_qc_forward_host": _int(ptr(abi.PgxQcConfig), ptr(abi.PgxQcWeights), ptr(abi.PgxQcIo), I32),
+    "pgx_qc_target_host": _int(ptr(abi.PgxQcConfig), ptr(abi.PgxQcWeights), ptr(abi.PgxQcIo), I32, I32),
+}
+
+# what load() requires of a library: a list the A/B tools filter before they load an older build
+EXPORTS = list(SIGNATURES)
 
 
 class PgxError(RuntimeError):
@@ -63,126 +160,10 @@ def load(path: str = None):
     for name in EXPORTS:
         if not hasattr(lib, name):
             raise PgxError(f"libpgx.so does not export {name}")
-    lib.pgx_version.restype = C.c_char_p
-    lib.pgx_last_error.restype = C.c_char_p
-    lib.pgx_obs_dim.argtypes = [C.POINTER(PgxConfig)]
-    lib.pgx_action_dim.argtypes = [C.POINTER(PgxConfig)]
-    lib.pgx_dev_model_bytes.argtypes = [C.POINTER(PgxConfig), C.c_void_p, C.c_int64]
-    lib.pgx_create.argtypes = [C.POINTER(PgxConfig), C.c_int, C.POINTER(C.c_void_p)]
-    lib.pgx_destroy.argtypes = [C.c_void_p]
-    lib.pgx_destroy.restype = None
-    lib.pgx_get_state.argtypes = [C.c_void_p, C.POINTER(PgxStateView)]
-    lib.pgx_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PgxStepOut), C.c_void_p]
-    lib.pgx_step.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PgxStepOut), C.c_void_p]
-    if hasattr(lib, "pgx_step_kernel"):   # (A/B runs load older builds with EXPORTS filtered)
-        lib.pgx_step_kernel.argtypes = [C.c_void_p]
-        lib.pgx_step_kernel.restype = C.c_char_p
-    lib.pgx_sample_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-    lib.pgx_compute_reward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_void_p,
-                                       C.c_void_p]
-    lib.pgx_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    lib.pgx_save_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.pgx_restore_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.pgx_snapshot.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
-    lib.pgx_restore.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-    lib.pgx_release.argtypes = [C.c_void_p, C.c_int32]
-    lib.pgx_set_rng_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.pgx_get_rng_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.pgx_replay_create.argtypes = [C.POINTER(PgxReplayConfig), C.c_int, C.POINTER(C.c_void_p)]
-    lib.pgx_replay_row_dim.argtypes = [C.POINTER(PgxReplayConfig)]
-    lib.pgx_replay_row_stride.argtypes = [C.POINTER(PgxReplayConfig)]
-    lib.pgx_replay_destroy.argtypes = [C.c_void_p]
-    lib.pgx_replay_destroy.restype = None
-    lib.pgx_replay_add.argtypes = [C.c_void_p, C.POINTER(PgxTransition), C.c_void_p]
-    lib.pgx_replay_size.argtypes = [C.c_void_p]
-    lib.pgx_replay_size.restype = C.c_int64
-    lib.pgx_replay_sample.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(PgxReplayBatch), C.c_void_p]
-    lib.pgx_replay_episode_arrays.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                              C.POINTER(C.c_void_p)]
-    lib.pgx_replay_set_last.argtypes = [C.c_void_p] * 5
-    lib.pgx_replay_collect.argtypes = [C.c_void_p, C.POINTER(PgxReplayStep), C.c_void_p]
-    lib.pgx_replay_truncate_last_trajectory.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-    lib.pgx_replay_state.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
-                                     C.c_int32, C.c_void_p]
-    lib.pgx_replay_arrays.argtypes = [C.c_void_p, C.POINTER(PgxReplayViews)]
-    lib.pgx_norm_create.argtypes = [C.POINTER(PgxNormConfig), C.c_int, C.POINTER(C.c_void_p)]
-    lib.pgx_norm_destroy.argtypes = [C.c_void_p]
-    lib.pgx_norm_destroy.restype = None
-    lib.pgx_norm_step.argtypes = [C.c_void_p, C.POINTER(PgxNormIo), C.c_void_p]
-    lib.pgx_norm_reset.argtypes = [C.c_void_p, C.POINTER(PgxNormIo), C.c_void_p]
-    lib.pgx_norm_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
-    lib.pgx_norm_apply.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    lib.pgx_norm_set_training.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-    lib.pgx_norm_set_keys.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-    lib.pgx_norm_get_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.pgx_norm_set_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.pgx_monitor_create.argtypes = [C.POINTER(PgxMonitorConfig), C.c_int, C.POINTER(C.c_void_p)]
-    lib.pgx_monitor_destroy.argtypes = [C.c_void_p]
-    lib.pgx_monitor_destroy.restype = None
-    lib.pgx_monitor_step.argtypes = [C.c_void_p, C.POINTER(PgxMonitorIo), C.c_void_p]
-    lib.pgx_monitor_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.pgx_monitor_clear.argtypes = [C.c_void_p, C.c_void_p]
-    lib.pgx_monitor_set_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.pgx_monitor_get_totals.argtypes = [C.c_void_p, C.POINTER(PgxMonitorTotals), C.c_void_p]
-    lib.pgx_monitor_read.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.POINTER(C.c_int32), C.c_void_p]
-    lib.pgx_monitor_get_env_state.argtypes = [C.c_void_p] * 6
-    lib.pgx_rollout_row_dim.argtypes = [C.POINTER(PgxRolloutConfig)]
-    lib.pgx_rollout_row_stride.argtypes = [C.POINTER(PgxRolloutConfig)]
-    lib.pgx_rollout_create.argtypes = [C.POINTER(PgxRolloutConfig), C.c_int, C.POINTER(C.c_void_p)]
-    lib.pgx_rollout_destroy.argtypes = [C.c_void_p]
-    lib.pgx_rollout_destroy.restype = None
-    lib.pgx_rollout_add.argtypes = [C.c_void_p, C.POINTER(PgxRolloutIo), C.c_void_p]
-    lib.pgx_rollout_compute_returns_and_advantage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.pgx_rollout_permutation.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.pgx_rollout_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PgxRolloutBatch), C.c_void_p]
-    lib.pgx_rollout_reset.argtypes = [C.c_void_p, C.c_void_p]
-    lib.pgx_rollout_set_last.argtypes = [C.c_void_p] * 6
-    lib.pgx_rollout_state.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int32, C.c_void_p]
-    lib.pgx_rollout_arrays.argtypes = [C.c_void_p, C.POINTER(PgxRolloutViews)]
-    lib.pgx_actor_create.argtypes = [C.POINTER(PgxActorConfig), C.c_int, C.POINTER(C.c_void_p)]
-    lib.pgx_actor_destroy.argtypes = [C.c_void_p]
-    lib.pgx_actor_destroy.restype = None
-    lib.pgx_actor_set_weights.argtypes = [C.c_void_p, C.POINTER(PgxActorWeights), C.c_void_p]
-    lib.pgx_actor_forward.argtypes = [C.c_void_p, C.POINTER(PgxActorIo), C.c_int32, C.c_void_p]
-    lib.pgx_actor_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
-    lib.pgx_actor_set_state.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-    lib.pgx_actor_forward_host.argtypes = [C.POINTER(PgxActorConfig), C.POINTER(PgxActorWeights), C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.pgx_ac_create.argtypes = [C.POINTER(PgxAcConfig), C.c_int, C.POINTER(C.c_void_p)]
-    lib.pgx_ac_destroy.argtypes = [C.c_void_p]
-    lib.pgx_ac_destroy.restype = None
-    lib.pgx_ac_set_weights.argtypes = [C.c_void_p, C.POINTER(PgxAcWeights), C.c_void_p]
-    lib.pgx_ac_forward.argtypes = [C.c_void_p, C.POINTER(PgxAcIo), C.c_int32, C.c_void_p]
-    lib.pgx_ac_values.argtypes = [C.c_void_p] * 7
-    lib.pgx_ac_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
-    lib.pgx_ac_set_state.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-    lib.pgx_ac_forward_host.argtypes = [C.POINTER(PgxAcConfig), C.POINTER(PgxAcWeights), C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.pgx_sde_actor_create.argtypes = [C.POINTER(PgxSdeActorConfig), C.c_int, C.POINTER(C.c_void_p)]
-    lib.pgx_sde_actor_destroy.argtypes = [C.c_void_p]
-    lib.pgx_sde_actor_destroy.restype = None
-    lib.pgx_sde_actor_set_weights.argtypes = [C.c_void_p, C.POINTER(PgxSdeActorWeights), C.c_void_p]
-    lib.pgx_sde_actor_reset_noise.argtypes = [C.c_void_p] * 4
-    lib.pgx_sde_actor_forward.argtypes = [C.c_void_p, C.POINTER(PgxSdeActorIo), C.c_int32, C.c_void_p]
-    lib.pgx_sde_actor_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
-    lib.pgx_sde_actor_set_state.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-    lib.pgx_sde_actor_get_matrices.argtypes = [C.c_void_p] * 3
-    lib.pgx_sde_actor_set_matrices.argtypes = [C.c_void_p] * 3
-    lib.pgx_sde_actor_get_std.argtypes = [C.c_void_p] * 3
-    lib.pgx_sde_actor_forward_host.argtypes = [C.POINTER(PgxSdeActorConfig), C.POINTER(PgxSdeActorWeights)] + \
-        [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3
-    lib.pgx_qc_create.argtypes = [C.POINTER(PgxQcConfig), C.c_int, C.POINTER(C.c_void_p)]
-    lib.pgx_qc_destroy.argtypes = [C.c_void_p]
-    lib.pgx_qc_destroy.restype = None
-    lib.pgx_qc_set_weights.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PgxQcWeights), C.c_void_p]
-    lib.pgx_qc_get_weights.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PgxQcWeights), C.c_void_p]
-    lib.pgx_qc_forward.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PgxQcIo), C.c_int32, C.c_void_p]
-    lib.pgx_qc_target.argtypes = [C.c_void_p, C.POINTER(PgxQcIo), C.c_int32, C.c_int32, C.c_void_p]
-    lib.pgx_qc_polyak.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
-    lib.pgx_qc_sync_target.argtypes = [C.c_void_p, C.c_void_p]
-    lib.pgx_qc_forward_host.argtypes = [C.POINTER(PgxQcConfig), C.POINTER(PgxQcWeights), C.POINTER(PgxQcIo), C.c_int32]
-    lib.pgx_qc_target_host.argtypes = [C.POINTER(PgxQcConfig), C.POINTER(PgxQcWeights), C.POINTER(PgxQcIo), C.c_int32,
-                                       C.c_int32]
+        fn = getattr(lib, name)
+        fn.argtypes, restype = SIGNATURES[name]
+        if restype is not INT:
+            fn.restype = restype
     _libs[path] = lib
     return lib
 

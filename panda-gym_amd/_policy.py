@@ -11,22 +11,16 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from ._native import PgxError, check, load
-
-try:
-    import torch
-except ImportError:  # pragma: no cover
-    torch = None
-
-OBS_KEYS = ("observation", "achieved_goal", "desired_goal")
+from ._handle import OBS_KEYS, Handle, torch  # noqa: F401  (OBS_KEYS, torch: importable from here as before)
+from ._native import PgxError, load
 
 
-class Policy:
-    """Base of the three policies.  A subclass sets ``_PREFIX`` (its C entry points' prefix) and ``_WHO``
+class Policy(Handle):
+    """Base of the four policies.  A subclass sets ``_PREFIX`` (its C entry points' prefix) and ``_WHO``
     (its name in a buffer-fit message), builds ``_cfg``, ``_names``, ``_w``, ``_b``, and defines ``_slots``,
     ``_push`` and ``forward_host``."""
 
-    _PREFIX = ""
+    _NEEDS = "its buffers"
     _WHO = "actor"
     _SD_PREFIX: Optional[str] = None   # keys of a whole policy's state dict to read, when it has any
 
@@ -48,47 +42,20 @@ class Policy:
         self._debug: Optional[Dict[str, "torch.Tensor"]] = None
         self._keep: List[Any] = []
 
-    @classmethod
-    def _need_torch(cls) -> None:
-        if torch is None:
-            raise PgxError(f"{cls.__name__} needs torch for its buffers")
-
-    def _lib_call(self, name: str, *args) -> None:
-        entry = f"{self._PREFIX}_{name}"
-        check(getattr(self.lib, entry)(*args), entry, self.lib)
-
     def _open(self, *host_extra) -> None:
         """The device handle with the parameters pushed; on a CPU device the library's argument checks
         either way: the host model on no rows."""
         if self.device.type == "cuda":
-            h = C.c_void_p()
-            torch.cuda.set_device(self.device)
-            self._lib_call("create", C.byref(self._cfg), self.device.index or 0, C.byref(h))
-            self._h = h
+            self._create(self._cfg)
             self._push()
         else:
             self.forward_host({"observation": np.zeros((0, self.obs_dim), np.float32),
                                "achieved_goal": np.zeros((0, 3), np.float32), "desired_goal": np.zeros((0, 3), np.float32)},
                               *host_extra)
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _need_device(self):
         if self._h is None:
             raise PgxError(f"this {type(self).__name__} has no device handle (device='cpu' or closed): no CPU fallback")
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            torch.cuda.synchronize(self.device)
-            getattr(self.lib, f"{self._PREFIX}_destroy")(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ----------------------------------------------------------- parameters
     def _pairs(self) -> List[Tuple[str, "torch.Tensor"]]:
@@ -133,6 +100,7 @@ class Policy:
 
     # --------------------------------------------------------- observations
     def _dev(self, x, shape) -> "torch.Tensor":
+        """Unlike ``Handle._dev``, no reshape: an input of another shape is refused."""
         t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
         if tuple(t.shape) != shape:
             raise ValueError(f"expected shape {list(shape)}, got {list(t.shape)}")
@@ -163,9 +131,9 @@ class Policy:
     def _get_word(self) -> int:
         self._need_device()
         v = C.c_uint64(0)
-        self._lib_call("state", self._h, C.byref(v), self._stream())
+        self._call("state", self._h, C.byref(v), self._stream())
         return int(v.value)
 
     def _set_word(self, value: int) -> None:
         self._need_device()
-        self._lib_call("set_state", self._h, C.c_uint64(int(value) & 0xFFFFFFFFFFFFFFFF), self._stream())
+        self._call("set_state", self._h, C.c_uint64(int(value) & 0xFFFFFFFFFFFFFFFF), self._stream())

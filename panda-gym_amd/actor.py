@@ -23,6 +23,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import abi
+from ._native import check
 from ._policy import OBS_KEYS, Policy, torch  # noqa: F401  (OBS_KEYS: importable from here as before)
 
 
@@ -88,7 +89,7 @@ class Actor(Policy):
 
     def _push(self) -> None:
         w = self._weights_struct([t.data_ptr() for t in self._w], [t.data_ptr() for t in self._b])
-        self._lib_call("set_weights", self._h, C.byref(w), self._stream())
+        self._call("set_weights", self._h, C.byref(w), self._stream())
 
     # ----------------------------------------------------------- parameters
     _slots = Policy._pairs
@@ -117,7 +118,7 @@ class Actor(Policy):
         io = abi.PgxActorIo(p(obs["observation"]), p(obs["achieved_goal"]), p(obs["desired_goal"]), p(self.actions),
                             p(eps), *([None] * 4 if d is None else [p(d[k]) for k in ("mean", "log_std", "eps", "philox")]))
         det = 1 if (deterministic or (self.kind == "deterministic" and self.action_noise is None)) else 0
-        self._lib_call("forward", self._h, C.byref(io), det, self._stream())
+        check(self.lib.pgx_actor_forward(self._h, C.byref(io), det, self._stream()), "pgx_actor_forward", self.lib)
 
     def __call__(self, obs: Dict[str, Any], deterministic: bool = False, eps: Any = None) -> "torch.Tensor":
         """Actions [N, A] for the observation dict ``obs`` (what ``step_tensors`` / ``reset_tensors`` of
@@ -140,7 +141,7 @@ class Actor(Policy):
         w = self._weights_struct([x.ctypes.data for x in ws], [x.ctypes.data for x in bs])
         mean = np.zeros((n, self.action_dim), np.float32)
         log_std = np.zeros((n, self.action_dim), np.float32) if self.kind == "gaussian" else None
-        self._lib_call("forward_host", C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
+        self._call("forward_host", C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
                        abi.ptr(o["achieved_goal"]), abi.ptr(o["desired_goal"]), n, abi.ptr(mean), abi.ptr(log_std))
         return mean, log_std
 

@@ -23,7 +23,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import abi
-from ._native import PgxError
+from ._native import PgxError, check
 from ._policy import Policy, torch
 
 DEFAULT_NET_ARCH = {"pi": (256, 256), "vf": (256, 256)}   # the reference's PPO setting
@@ -117,7 +117,7 @@ class ActorCritic(Policy):
     def _push(self) -> None:
         w = self._weights_struct([t.data_ptr() for t in self._w], [t.data_ptr() for t in self._b],
                                  self._log_std_lib.data_ptr())
-        self._lib_call("set_weights", self._h, C.byref(w), self._stream())
+        self._call("set_weights", self._h, C.byref(w), self._stream())
 
     # ----------------------------------------------------------- parameters
     def _slots(self):
@@ -155,11 +155,12 @@ class ActorCritic(Policy):
         io = abi.PgxAcIo(p(obs["observation"]), p(obs["achieved_goal"]), p(obs["desired_goal"]), p(self.actions),
                          p(self.clipped_actions), p(self.values), p(self.log_probs), p(eps),
                          *([None] * 3 if d is None else [p(d[k]) for k in ("mean", "eps", "philox")]))
-        self._lib_call("forward", self._h, C.byref(io), 1 if deterministic else 0, self._stream())
+        check(self.lib.pgx_ac_forward(self._h, C.byref(io), 1 if deterministic else 0, self._stream()), "pgx_ac_forward",
+              self.lib)
 
     def _launch_values(self, obs: Dict[str, "torch.Tensor"], need: Optional["torch.Tensor"], out: "torch.Tensor") -> None:
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        self._lib_call("values", self._h, p(obs["observation"]), p(obs["achieved_goal"]), p(obs["desired_goal"]),
+        self._call("values", self._h, p(obs["observation"]), p(obs["achieved_goal"]), p(obs["desired_goal"]),
                        p(need), p(out), self._stream())
 
     def __call__(self, obs: Dict[str, Any], deterministic: bool = False, eps: Any = None):
@@ -212,7 +213,7 @@ class ActorCritic(Policy):
         w = self._weights_struct([x.ctypes.data for x in ws], [x.ctypes.data for x in bs], ls.ctypes.data)
         mean = np.zeros((n, self.action_dim), np.float32)
         value = np.zeros((n,), np.float32)
-        self._lib_call("forward_host", C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
+        self._call("forward_host", C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
                        abi.ptr(o["achieved_goal"]), abi.ptr(o["desired_goal"]), n, abi.ptr(mean), abi.ptr(value))
         return mean, value
 

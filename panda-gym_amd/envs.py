@@ -27,13 +27,9 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import abi, reach_ao
+from ._handle import Handle, _view, torch  # noqa: F401  (_view: importable from here as before)
 from ._native import PgxError, check, load
 from .model import load_model
-
-try:
-    import torch
-except ImportError:  # pragma: no cover - torch is part of the image
-    torch = None
 
 
 # ------------------------------------------------- gymnasium / SB3 identity
@@ -218,7 +214,7 @@ def pcg64_from_record(rec: np.ndarray) -> np.random.Generator:
 
 
 # ------------------------------------------------------------ vec env
-class PandaVecEnv(_VecEnvBase):
+class PandaVecEnv(Handle, _VecEnvBase):
     """N independent Panda envs stepped in lockstep by one HIP kernel launch (an SB3 ``VecEnv``
     subclass where stable-baselines3 imports).
 
@@ -244,6 +240,8 @@ class PandaVecEnv(_VecEnvBase):
     arithmetic (``reach_ao.reset_draws``), so it takes the same branches and draws; its goal agrees
     to a few ulp (the device's sin / cos / cbrt against the host libm)."""
 
+    _PREFIX = "pgx"
+    _LIVES = "runs on a HIP device only (no CPU physics fallback)"
     metadata = {"render_modes": []}
     render_mode = None
     _pre_sync = None   # set by VecMonitor.step_wait for its own call: runs before step_wait's synchronise
@@ -274,8 +272,7 @@ class PandaVecEnv(_VecEnvBase):
         paths that look (``step_wait``, ``raise_device_errors``) raise PgxError naming the envs."""
         if nonfinite not in NONFINITE_MODES:
             raise ValueError(f"nonfinite must be one of {NONFINITE_MODES}, got {nonfinite!r}")
-        if torch is None:
-            raise PgxError("PandaVecEnv needs torch for device buffers")
+        self._need_torch()
         self.lib = load(lib_path)
         self.env_id = env_id
         base_spec = spec(env_id)
@@ -285,9 +282,7 @@ class PandaVecEnv(_VecEnvBase):
             base_spec = replace(base_spec, max_episode_steps=max_episode_steps)
         self.spec = base_spec
         self.num_envs = int(num_envs)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise PgxError("PandaVecEnv runs on a HIP device only (no CPU physics fallback)")
+        self._on_device(device)
         self._model = abi.make_model(load_model(model_name), ee_link=11)
         self._params = abi.default_sim_params(n_substeps=n_substeps)
         for k, v in (sim_params or {}).items():
@@ -327,10 +322,7 @@ class PandaVecEnv(_VecEnvBase):
         self.nonfinite_resets = 0   # caught env-steps the host paths have seen (step_wait, raise_device_errors)
         self.obs_dim =self.lib.pgx_obs_dim(C.byref(self._cfg))
         self.action_dim = self.lib.pgx_action_dim(C.byref(self._cfg))
-        h = C.c_void_p()
-        torch.cuda.set_device(self.device)
-        self._check(self.lib.pgx_create(C.byref(self._cfg), self.device.index or 0, C.byref(h)), "pgx_create")
-        self._h = h
+        self._create(self._cfg)
         self.seed_value = seed
         n, od = self.num_envs, self.obs_dim
         kw = dict(device=self.device)
@@ -385,28 +377,13 @@ class PandaVecEnv(_VecEnvBase):
     def _check(self, rc: int, what: str) -> None:
         check(rc, what, self.lib)
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            torch.cuda.synchronize(self.device)
-            self.lib.pgx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def state(self) -> Dict[str, torch.Tensor]:
         """Device views of the SoA state (q, qd [7,N] f32; qc [7,N] f32 the pose getLinkState reports;
         goal [3,N] f64; object [13,N] f32 =
         pos, quat (x,y,z,w), linvel, angvel; contacts [2 * abi.CONTACT_SLOTS, N] f32 warm-start cache
         (feature id, normal impulse): object-scene slots, then robot slots; elapsed, episode [N])."""
         v = abi.PgxStateView()
-        self._check(self.lib.pgx_get_state(self._h, C.byref(v)), "pgx_get_state")
+        self._call("get_state", self._h, C.byref(v))
         n = self.num_envs
         return {
             "q": _view(v.q, (7, n), torch.float32, self.device),
@@ -432,7 +409,7 @@ class PandaVecEnv(_VecEnvBase):
         """Robot contact points this handle's kernels keep per env (the deepest of Bullet's <= 4 per
         colliding pair; abi.ROBOT_POINTS / ROBOT_POINTS_ARM / ROBOT_POINTS_ONE_LANE; 0 without contacts)."""
         v = abi.PgxStateView()
-        self._check(self.lib.pgx_get_state(self._h, C.byref(v)), "pgx_get_state")
+        self._call("get_state", self._h, C.byref(v))
         return int(v.robot_points)
 
     def raise_device_errors(self, errors: Optional[int] = None, caught: Optional[np.ndarray] = None) -> None:
@@ -472,16 +449,14 @@ class PandaVecEnv(_VecEnvBase):
 
     def _set_rng_streams(self, records: np.ndarray) -> None:
         rec = torch.as_tensor(np.ascontiguousarray(records, dtype=np.uint64).view(np.int64), device=self.device)
-        self._check(self.lib.pgx_set_rng_streams(self._h, C.c_void_p(rec.data_ptr()), self._stream()),
-                    "pgx_set_rng_streams")
+        self._call("set_rng_streams", self._h, C.c_void_p(rec.data_ptr()), self._stream())
         self._rng_keep = rec   # read by the queued copy
 
     def rng_streams(self) -> np.ndarray:
         """[N, abi.PCG64_WORDS] uint64 PCG64 records of the envs' reset streams (``reset_rng="pcg64"``):
         where each env's np_random stands (pcg64_from_record rebuilds the numpy Generator)."""
         out = torch.empty((self.num_envs, abi.PCG64_WORDS), dtype=torch.int64, device=self.device)
-        self._check(self.lib.pgx_get_rng_streams(self._h, C.c_void_p(out.data_ptr()), self._stream()),
-                    "pgx_get_rng_streams")
+        self._call("get_rng_streams", self._h, C.c_void_p(out.data_ptr()), self._stream())
         return out.cpu().numpy().view(np.uint64)
 
     def reset_tensors(self, seed: Optional[int] = None, mask: Optional[torch.Tensor] = None,
@@ -519,10 +494,9 @@ class PandaVecEnv(_VecEnvBase):
         m = None
         if mask is not None:
             m = mask.to(device=self.device, dtype=torch.uint8).contiguous()
-        self._check(self.lib.pgx_reset(self._h, None if m is None else C.c_void_p(m.data_ptr()),
-                                 None if inj is None else C.c_void_p(inj.data_ptr()),
-                                 None if inj_obj is None else C.c_void_p(inj_obj.data_ptr()), C.byref(self._out),
-                                 self._stream()), "pgx_reset")
+        self._call("reset", self._h, None if m is None else C.c_void_p(m.data_ptr()),
+                   None if inj is None else C.c_void_p(inj.data_ptr()),
+                   None if inj_obj is None else C.c_void_p(inj_obj.data_ptr()), C.byref(self._out), self._stream())
         self._keep = (m, inj, inj_obj)  # keep the buffers alive until the stream consumes them
         if episode_phase == "staggered":   # stream-ordered after the reset (torch's current stream)
             T = int(self.spec.max_episode_steps)
@@ -716,9 +690,8 @@ class PandaVecEnv(_VecEnvBase):
         dg = dg.to(self.device, torch.float32).reshape(-1, 3).contiguous()
         out = torch.empty(ag.shape[0], dtype=torch.float32, device=self.device)
         rt = abi.REWARD_CODES[self.reward_type]
-        self._check(self.lib.pgx_compute_reward(C.c_void_p(ag.data_ptr()), C.c_void_p(dg.data_ptr()),
-                                          C.c_int64(ag.shape[0]), rt, C.c_double(self.distance_threshold),
-                                          C.c_void_p(out.data_ptr()), self._stream()), "pgx_compute_reward")
+        self._call("compute_reward", C.c_void_p(ag.data_ptr()), C.c_void_p(dg.data_ptr()), C.c_int64(ag.shape[0]), rt,
+                   C.c_double(self.distance_threshold), C.c_void_p(out.data_ptr()), self._stream())
         out = out.reshape(shape)
         return out.cpu().numpy() if is_np else out
 
@@ -746,32 +719,21 @@ class PandaVecEnv(_VecEnvBase):
         PyBullet.save_state, pybullet.py:79-86): the id is libpgx's, the first non-negative
         integer not in use."""
         sid = C.c_int32()
-        self._check(self.lib.pgx_snapshot(self._h, C.byref(sid), self._stream()), "pgx_snapshot")
+        self._call("snapshot", self._h, C.byref(sid), self._stream())
         return int(sid.value)
 
     def restore_state(self, state_id: int) -> None:
         """Restore a snapshot; an id that was removed (or never saved) raises PgxError, as
         pybullet.error in the reference (test/save_and_restore_test.py:30-36)."""
-        self._check(self.lib.pgx_restore(self._h, int(state_id), self._stream()), "pgx_restore")
+        self._call("restore", self._h, int(state_id), self._stream())
 
     def remove_state(self, state_id: int) -> None:
         """Free a snapshot; its id becomes available again (PyBullet.remove_state, pybullet.py:96-102)."""
-        self._check(self.lib.pgx_release(self._h, int(state_id)), "pgx_release")
+        self._call("release", self._h, int(state_id))
 
 
 NONFINITE_MODES = ("off", "reset", "raise")
 _INFO_TEMPLATES = [{"is_success": s, "is_truncated": c} for c in (False, True) for s in (False, True)]
-
-
-def _view(addr: int, shape, dtype, device):
-    """Wrap a libpgx-owned device buffer as a torch tensor (no copy)."""
-    typestr = {torch.float32: "<f4", torch.float64: "<f8", torch.int32: "<i4", torch.int64: "<i8"}[dtype]
-
-    class _Iface:  # torch has no public from-pointer constructor; use __cuda_array_interface__
-        __cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(addr), False),
-                                    "version": 2, "strides": None}
-
-    return torch.as_tensor(_Iface(), device=device)
 
 
 # --------------------------------------------------------- single env

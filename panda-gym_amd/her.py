@@ -30,12 +30,8 @@ from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Union
 import numpy as np
 
 from . import abi
+from ._handle import Handle, _view, resolve_dims, torch
 from ._native import PgxError, check, load
-
-try:
-    import torch
-except ImportError:  # pragma: no cover
-    torch = None
 
 STRATEGIES = {"future": abi.HER_FUTURE, "final": abi.HER_FINAL, "episode": abi.HER_EPISODE}
 
@@ -50,12 +46,14 @@ class DictReplayBufferSamples(NamedTuple):
     rewards: "torch.Tensor"
 
 
-class HerReplayBuffer:
+class HerReplayBuffer(Handle):
     """SB3 HerReplayBuffer over a device ring of ``buffer_size // n_envs`` slots x ``n_envs``.
 
     ``env`` may be a ``PandaVecEnv`` (reward type, threshold and dims are read
     from it, as SB3 reads them through ``env.env_method("compute_reward")``).
     """
+
+    _PREFIX = "pgx_replay"
 
     def __init__(self, buffer_size: int, observation_space: Any = None, action_space: Any = None, env: Any = None,
                  device: Any = "cuda:0", n_envs: int = 1, n_sampled_goal: int = 4,
@@ -63,31 +61,19 @@ class HerReplayBuffer:
                  handle_timeout_termination: bool = True, seed: int = 0, obs_dim: Optional[int] = None,
                  action_dim: Optional[int] = None, reward_type: Optional[str] = None,
                  distance_threshold: Optional[float] = None):
-        if torch is None:
-            raise PgxError("HerReplayBuffer needs torch for device buffers")
+        self._need_torch()
         if goal_selection_strategy not in STRATEGIES:
             raise ValueError(f"Invalid goal selection strategy, please use one of {list(STRATEGIES)}")
         if copy_info_dict:
             raise NotImplementedError("copy_info_dict: infos are not needed by Task.compute_reward")
         self.lib = load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise PgxError("HerReplayBuffer lives on a HIP device only (no CPU fallback)")
+        self._on_device(device)
         if env is not None:
-            n_envs = env.num_envs
-            obs_dim = env.obs_dim if obs_dim is None else obs_dim
-            action_dim = env.action_dim if action_dim is None else action_dim
             reward_type = env.reward_type if reward_type is None else reward_type
             distance_threshold = env.distance_threshold if distance_threshold is None else distance_threshold
-        if observation_space is not None and obs_dim is None:
-            obs_dim = int(np.prod(observation_space["observation"].shape))
-        if action_space is not None and action_dim is None:
-            action_dim = int(np.prod(action_space.shape))
-        if obs_dim is None or action_dim is None:
-            raise ValueError("obs_dim/action_dim: pass env, the spaces, or the dims")
-        self.n_envs = int(n_envs)
+        self.n_envs, self.obs_dim, self.action_dim = resolve_dims(env, observation_space, action_space, n_envs, obs_dim,
+                                                                  action_dim)
         self.buffer_size = max(int(buffer_size) // self.n_envs, 1)   # SB3 BaseBuffer: per-env slots
-        self.obs_dim, self.action_dim = int(obs_dim), int(action_dim)
         self.reward_type = reward_type or "sparse"
         self.distance_threshold = 0.05 if distance_threshold is None else float(distance_threshold)
         self.n_sampled_goal = n_sampled_goal
@@ -106,40 +92,15 @@ class HerReplayBuffer:
         self.row_stride = self.lib.pgx_replay_row_stride(C.byref(cfg))
         if self.lib.pgx_replay_row_dim(C.byref(cfg)) != self.row_dim:
             raise PgxError("libpgx batch row layout differs from abi.replay_row_fields")
-        h = C.c_void_p()
-        torch.cuda.set_device(self.device)
-        check(self.lib.pgx_replay_create(C.byref(cfg), self.device.index or 0, C.byref(h)), "pgx_replay_create")
-        self._h = h
+        self._create(cfg)
         self._draw = 0
         self._seen_valid = False
         self._keep: List[Any] = []
 
     # ------------------------------------------------------------ plumbing
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            torch.cuda.synchronize(self.device)
-            self.lib.pgx_replay_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _dev(self, x, shape, dtype) -> "torch.Tensor":
-        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-        t = t.to(device=self.device, dtype=dtype).reshape(shape).contiguous()
-        return t
-
     def _arrays(self):
         s, l, nv = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        check(self.lib.pgx_replay_episode_arrays(self._h, C.byref(s), C.byref(l), C.byref(nv)),
-              "pgx_replay_episode_arrays")
-        from .envs import _view
+        self._call("episode_arrays", self._h, C.byref(s), C.byref(l), C.byref(nv))
         shp = (self.buffer_size, self.n_envs)
         return _view(s.value, shp, torch.int32, self.device), _view(l.value, shp, torch.int32, self.device), \
             _view(nv.value, (1,), torch.int32, self.device)
@@ -156,8 +117,7 @@ class HerReplayBuffer:
     def _state(self, clear: bool = False):
         """(added, n_valid, errors) from the device words: one sync; refreshes libpgx's host mirror."""
         added, nv, err = C.c_int64(0), C.c_int32(0), C.c_uint32(0)
-        check(self.lib.pgx_replay_state(self._h, C.byref(added), C.byref(nv), C.byref(err), 1 if clear else 0,
-                                        self._stream()), "pgx_replay_state")
+        self._call("state", self._h, C.byref(added), C.byref(nv), C.byref(err), 1 if clear else 0, self._stream())
         return int(added.value), int(nv.value), int(err.value)
 
     @property
@@ -175,10 +135,7 @@ class HerReplayBuffer:
 
     def raise_device_errors(self) -> None:
         """Raise what the kernels flagged in the sticky device word and clear it (one sync)."""
-        err = self._state(clear=True)[2]
-        if err:
-            names = [msg for bit, msg in abi.REPLAY_ERRORS.items() if err & bit]
-            raise PgxError("; ".join(names) if names else f"replay device error flags 0x{err:x}")
+        self._raise_flags(self._state(clear=True)[2], abi.REPLAY_ERRORS, "replay")
 
     def arrays(self) -> Dict[str, "torch.Tensor"]:
         """Device views of everything stored: ``records`` [C, N, record_stride] and the fields as
@@ -187,10 +144,8 @@ class HerReplayBuffer:
         ``last_achieved_goal`` / ``last_desired_goal`` [N, 3] (views into ``carry`` [N,
         carry_stride]), ``ep_start`` / ``ep_length`` [C, N], ``cur_ep_start`` [N] and the words
         ``n_valid``, ``added`` (int64), ``errors``, ``carry_set`` [1]."""
-        from .envs import _view
-
         v = abi.PgxReplayViews()
-        check(self.lib.pgx_replay_arrays(self._h, C.byref(v)), "pgx_replay_arrays")
+        self._call("arrays", self._h, C.byref(v))
         Cn, N, od, R, W, dev = self.buffer_size, self.n_envs, self.obs_dim, int(v.record_stride), \
             int(v.carry_stride), self.device
         rec = _view(v.records, (Cn, N, R), torch.float32, dev)
@@ -223,7 +178,7 @@ class HerReplayBuffer:
         if timeout is not None and self.handle_timeout_termination:
             to = self._dev(timeout, (N,), u8)
         tr = abi.PgxTransition(*[x.data_ptr() for x in t], None if to is None else to.data_ptr())
-        check(self.lib.pgx_replay_add(self._h, C.byref(tr), self._stream()), "pgx_replay_add")
+        self._call("add", self._h, C.byref(tr), self._stream())
         self._keep = t + [to]  # alive until the stream has consumed them (same-stream allocator reuse is safe)
 
     def add(self, obs: Dict[str, Any], next_obs: Dict[str, Any], action, reward, done,
@@ -266,14 +221,13 @@ class HerReplayBuffer:
         f = torch.float32
         t = [self._dev(obs["observation"], (N, self.obs_dim), f), self._dev(obs["achieved_goal"], (N, 3), f),
              self._dev(obs["desired_goal"], (N, 3), f)]
-        check(self.lib.pgx_replay_set_last(self._h, *[C.c_void_p(x.data_ptr()) for x in t], self._stream()),
-              "pgx_replay_set_last")
+        self._call("set_last", self._h, *[C.c_void_p(x.data_ptr()) for x in t], self._stream())
         self._keep_last = t   # read by the queued launch
 
     def _launch_collect(self, action, reward, terminated, truncated, obs, ag, dg, tobs, tag, tdg) -> None:
         io = abi.PgxReplayStep(*[x.data_ptr() for x in (action, reward, terminated, truncated, obs, ag, dg, tobs, tag,
                                                         tdg)], 1 if self.handle_timeout_termination else 0, 0)
-        check(self.lib.pgx_replay_collect(self._h, C.byref(io), self._stream()), "pgx_replay_collect")
+        check(self.lib.pgx_replay_collect(self._h, C.byref(io), self._stream()), "pgx_replay_collect", self.lib)
 
     def collect_tensors(self, action, reward, obs: Dict[str, Any], terminated, truncated,
                         terminal_obs: Dict[str, Any]) -> None:
@@ -360,8 +314,7 @@ class HerReplayBuffer:
         stands, so that its transitions become valid and no relabelled goal is drawn across it.
         Call it after a forced ``reset_tensors()``, an env switch or the end of a ``learn()``, then
         ``set_last(obs)``.  A no-op for envs at an episode start."""
-        check(self.lib.pgx_replay_truncate_last_trajectory(self._h, 1 if self.handle_timeout_termination else 0,
-                                                           self._stream()), "pgx_replay_truncate_last_trajectory")
+        self._call("truncate_last_trajectory", self._h, 1 if self.handle_timeout_termination else 0, self._stream())
 
     # --------------------------------------------------------------- sample
     def alloc_batch(self, batch_size: int, with_indices: bool = True) -> Dict[str, "torch.Tensor"]:
@@ -391,7 +344,7 @@ class HerReplayBuffer:
         ptr = lambda k: out[k].data_ptr() if out.get(k) is not None else None  # noqa: E731
         b = abi.PgxReplayBatch(rows.data_ptr(), ptr("slot"), ptr("env"), ptr("goal_slot"))
         check(self.lib.pgx_replay_sample(self._h, C.c_int64(rows.shape[0]), C.c_uint64(d), C.byref(b),
-                                         self._stream()), "pgx_replay_sample")
+                                         self._stream()), "pgx_replay_sample", self.lib)
         if not self._seen_valid:
             # SB3 raises before the first episode has ended; check once (one sync) until it has
             if int(self._arrays()[2].item()) == 0:

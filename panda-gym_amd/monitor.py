@@ -24,13 +24,9 @@ from typing import Any, Callable, Dict, Optional, Sequence
 import numpy as np
 
 from . import abi
-from ._native import PgxError, check, load
+from ._handle import Handle, torch
+from ._native import check, load
 from .normalize import VecNormalize
-
-try:
-    import torch
-except ImportError:  # pragma: no cover - torch is part of the image
-    torch = None
 
 TOTALS_INT = ("episodes", "length_sum", "length_sum_success", "steps", "envs_open")
 STATS_LAYOUT = ("episodes", "successes", "return_sum", "length_sum")   # stats_vector(), shard.gather_stats
@@ -87,40 +83,19 @@ def episode_count_targets(n_eval_episodes: int, n_envs: int) -> np.ndarray:
     return np.array([(int(n_eval_episodes) + i) // int(n_envs) for i in range(int(n_envs))], dtype=np.int32)
 
 
-class EpisodeMonitor:
+class EpisodeMonitor(Handle):
     """One pgx_monitor handle for ``n_envs`` envs on ``device``: per-env return / length / speed
     accumulators, the ring of the newest ``window`` finished episodes, totals and quota."""
 
+    _PREFIX = "pgx_monitor"
+
     def __init__(self, n_envs: int, obs_dim: int, window: int = 100, speed_col: int = 3, device: Any = "cuda:0",
                  lib=None):
-        if torch is None:
-            raise PgxError("EpisodeMonitor needs torch for device buffers")
+        self._need_torch()
         self.lib = lib or load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise PgxError("EpisodeMonitor lives on a HIP device only (no CPU fallback)")
+        self._on_device(device)
         self.n_envs, self.obs_dim, self.window, self.speed_col = int(n_envs), int(obs_dim), int(window), int(speed_col)
-        cfg = abi.PgxMonitorConfig(self.n_envs, self.obs_dim, self.window, self.speed_col)
-        h = C.c_void_p()
-        torch.cuda.set_device(self.device)
-        check(self.lib.pgx_monitor_create(C.byref(cfg), self.device.index or 0, C.byref(h)), "pgx_monitor_create",
-              self.lib)
-        self._h = h
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            torch.cuda.synchronize(self.device)
-            self.lib.pgx_monitor_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(abi.PgxMonitorConfig(self.n_envs, self.obs_dim, self.window, self.speed_col))
 
     # ------------------------------------------------------------ launches
     def step(self, io: abi.PgxMonitorIo) -> None:
@@ -134,13 +109,12 @@ class EpisodeMonitor:
             m = mask.to(device=self.device, dtype=torch.uint8).contiguous()
             if tuple(m.shape) != (self.n_envs,):
                 raise ValueError(f"mask must have shape ({self.n_envs},), got {tuple(m.shape)}")
-        check(self.lib.pgx_monitor_reset(self._h, None if m is None else C.c_void_p(m.data_ptr()), self._stream()),
-              "pgx_monitor_reset", self.lib)
+        self._call("reset", self._h, None if m is None else C.c_void_p(m.data_ptr()), self._stream())
         self._keep_mask = m   # read by the queued launch
 
     def clear(self) -> None:
         """Back to the state after construction (the targets stay)."""
-        check(self.lib.pgx_monitor_clear(self._h, self._stream()), "pgx_monitor_clear", self.lib)
+        self._call("clear", self._h, self._stream())
 
     def set_targets(self, targets: Optional[Sequence[int]]) -> None:
         """Per-env episode quota (None: none): an env that has reached it is no longer recorded."""
@@ -149,14 +123,13 @@ class EpisodeMonitor:
             t = np.ascontiguousarray(targets, dtype=np.int32)
             if t.shape != (self.n_envs,):
                 raise ValueError(f"targets must have shape ({self.n_envs},), got {t.shape}")
-        check(self.lib.pgx_monitor_set_targets(self._h, abi.ptr(t), self._stream()), "pgx_monitor_set_targets",
-              self.lib)
+        self._call("set_targets", self._h, abi.ptr(t), self._stream())
 
     # ------------------------------------------------------------- read-out
     def totals(self) -> Dict[str, Any]:
         """pgx_monitor_totals as a dict (``outcomes``: a list by ``abi.EP_*``).  Synchronises."""
         t = abi.PgxMonitorTotals()
-        check(self.lib.pgx_monitor_get_totals(self._h, C.byref(t), self._stream()), "pgx_monitor_get_totals", self.lib)
+        self._call("get_totals", self._h, C.byref(t), self._stream())
         out: Dict[str, Any] = {k: int(getattr(t, k)) for k in TOTALS_INT}
         out["outcomes"] = [int(x) for x in t.outcomes]
         out["return_sum"], out["speed_sum_success"] = float(t.return_sum), float(t.speed_sum_success)
@@ -169,9 +142,8 @@ class EpisodeMonitor:
         a = {"r": np.zeros(m, np.float32), "l": np.zeros(m, np.int32), "env": np.zeros(m, np.int32),
              "outcome": np.zeros(m, np.int32), "step": np.zeros(m, np.int64), "speed_sum": np.zeros(m, np.float64)}
         n = C.c_int32(0)
-        check(self.lib.pgx_monitor_read(self._h, m, *[abi.ptr(a[k]) for k in ("r", "l", "env", "outcome", "step",
-                                                                              "speed_sum")], C.byref(n),
-                                        self._stream()), "pgx_monitor_read", self.lib)
+        self._call("read", self._h, m, *[abi.ptr(a[k]) for k in ("r", "l", "env", "outcome", "step", "speed_sum")],
+                   C.byref(n), self._stream())
         return {k: v[:n.value].copy() for k, v in a.items()}
 
     def env_state(self) -> Dict[str, np.ndarray]:
@@ -179,15 +151,11 @@ class EpisodeMonitor:
         n = self.n_envs
         a = {"ret": np.zeros(n, np.float32), "len": np.zeros(n, np.int32), "speed": np.zeros(n, np.float64),
              "ep_count": np.zeros(n, np.int32)}
-        check(self.lib.pgx_monitor_get_env_state(self._h, *[abi.ptr(a[k]) for k in ("ret", "len", "speed", "ep_count")],
-                                                 self._stream()), "pgx_monitor_get_env_state", self.lib)
+        self._call("get_env_state", self._h, *[abi.ptr(a[k]) for k in ("ret", "len", "speed", "ep_count")],
+                   self._stream())
         return a
 
     # ------------------------------------------- array-level step (tests, tools)
-    def _dev(self, x, shape, dtype):
-        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-        return t.to(device=self.device, dtype=dtype).reshape(shape).contiguous()
-
     def step_arrays(self, reward, success, terminated, truncated, obs=None, terminal_obs=None, task_truncated=None,
                     nonfinite=None):
         """One pgx_monitor_step over host or device arrays (copied to fresh device buffers): returns

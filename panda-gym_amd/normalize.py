@@ -23,12 +23,8 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import abi
-from ._native import PgxError, check, load
-
-try:
-    import torch
-except ImportError:  # pragma: no cover - torch is part of the image
-    torch = None
+from ._handle import Handle, torch
+from ._native import check, load
 
 KEYS = abi.NORM_KEYS
 
@@ -56,47 +52,28 @@ class RunningMeanStd:
         return f"RunningMeanStd(mean={self.mean!r}, var={self.var!r}, count={self.count!r})"
 
 
-class Normalizer:
+class Normalizer(Handle):
     """One pgx_norm handle: statistics of ``obs_dim + 6`` observation columns (observation,
     achieved_goal, desired_goal) and of the returns, on ``device``."""
+
+    _PREFIX = "pgx_norm"
 
     def __init__(self, n_envs: int, obs_dim: int, device: Any = "cuda:0", keys: int = abi.NORM_KEY_ALL,
                  norm_reward: bool = True, clip_obs: float = 10.0, clip_reward: float = 10.0, gamma: float = 0.99,
                  epsilon: float = 1e-8, training: bool = True, lib=None):
-        if torch is None:
-            raise PgxError("Normalizer needs torch for device buffers")
+        self._need_torch()
         self.lib = lib or load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise PgxError("Normalizer lives on a HIP device only (no CPU fallback)")
+        self._on_device(device)
         self.n_envs, self.obs_dim = int(n_envs), int(obs_dim)
         self.columns = self.obs_dim + 6
         cfg = abi.PgxNormConfig(self.n_envs, self.obs_dim, int(keys), 1 if norm_reward else 0, float(clip_obs),
                                 float(clip_reward), float(gamma), float(epsilon))
         self._cfg = cfg
         self.keys, self.norm_reward = int(keys), bool(norm_reward)
-        h = C.c_void_p()
-        torch.cuda.set_device(self.device)
-        check(self.lib.pgx_norm_create(C.byref(cfg), self.device.index or 0, C.byref(h)), "pgx_norm_create", self.lib)
-        self._h = h
+        self._create(cfg)
         self.training = True
         if not training:
             self.set_training(False)
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            torch.cuda.synchronize(self.device)
-            self.lib.pgx_norm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ------------------------------------------------------------ launches
     def step(self, io: abi.PgxNormIo) -> None:
@@ -104,14 +81,14 @@ class Normalizer:
         check(self.lib.pgx_norm_step(self._h, C.byref(io), self._stream()), "pgx_norm_step", self.lib)
 
     def reset(self, io: abi.PgxNormIo) -> None:
-        check(self.lib.pgx_norm_reset(self._h, C.byref(io), self._stream()), "pgx_norm_reset", self.lib)
+        self._call("reset", self._h, C.byref(io), self._stream())
 
     def rows(self, rows: "torch.Tensor", action_dim: int) -> None:
         """Normalise a HER batch ``rows`` [B, row_stride] (include/pgx.h layout) in place."""
         if rows.dtype != torch.float32 or rows.device != self.device or not rows.is_contiguous() or rows.dim() != 2:
             raise ValueError(f"rows must be a contiguous f32 [B, row_stride] tensor on {self.device}")
-        check(self.lib.pgx_norm_rows(self._h, C.c_void_p(rows.data_ptr()), C.c_int64(rows.shape[0]), int(action_dim),
-                                     int(rows.shape[1]), self._stream()), "pgx_norm_rows", self.lib)
+        self._call("rows", self._h, C.c_void_p(rows.data_ptr()), C.c_int64(rows.shape[0]), int(action_dim),
+                   int(rows.shape[1]), self._stream())
 
     normalize_rows = rows   # what HerReplayBuffer.sample_into(..., env=) calls
 
@@ -123,19 +100,17 @@ class Normalizer:
         if key != abi.NORM_REWARD and (a.dim() == 0 or a.shape[-1] != w):
             raise ValueError(f"{KEYS[key]} arrays must end in {w} columns, got shape {tuple(a.shape)}")
         out = torch.empty_like(a)
-        check(self.lib.pgx_norm_apply(self._h, int(key), 1 if inverse else 0, C.c_void_p(a.data_ptr()),
-                                      C.c_void_p(out.data_ptr()), C.c_int64(a.numel() // w), self._stream()),
-              "pgx_norm_apply", self.lib)
+        self._call("apply", self._h, int(key), 1 if inverse else 0, C.c_void_p(a.data_ptr()), C.c_void_p(out.data_ptr()),
+                   C.c_int64(a.numel() // w), self._stream())
         self._keep = a   # read by the queued launch
         return out
 
     def set_training(self, training: bool) -> None:
-        check(self.lib.pgx_norm_set_training(self._h, 1 if training else 0, self._stream()), "pgx_norm_set_training",
-              self.lib)
+        self._call("set_training", self._h, 1 if training else 0, self._stream())
         self.training = bool(training)
 
     def set_keys(self, keys: int, norm_reward: bool) -> None:
-        check(self.lib.pgx_norm_set_keys(self._h, int(keys), 1 if norm_reward else 0), "pgx_norm_set_keys", self.lib)
+        self._call("set_keys", self._h, int(keys), 1 if norm_reward else 0)
         self.keys, self.norm_reward = int(keys), bool(norm_reward)
 
     # ---------------------------------------------------------- statistics
@@ -144,8 +119,7 @@ class Normalizer:
         S = self.columns + 1
         mean, var, count = np.empty(S), np.empty(S), np.empty(S)
         ret = np.empty(self.n_envs)
-        check(self.lib.pgx_norm_get_stats(self._h, abi.ptr(mean), abi.ptr(var), abi.ptr(count), abi.ptr(ret),
-                                          self._stream()), "pgx_norm_get_stats", self.lib)
+        self._call("get_stats", self._h, abi.ptr(mean), abi.ptr(var), abi.ptr(count), abi.ptr(ret), self._stream())
         return mean, var, count, ret
 
     def set_stats(self, mean, var, count, returns=None) -> None:
@@ -159,8 +133,8 @@ class Normalizer:
             ret = np.ascontiguousarray(returns, dtype=np.float64)
             if ret.shape != (self.n_envs,):
                 raise ValueError(f"returns must have shape ({self.n_envs},), got {ret.shape}")
-        check(self.lib.pgx_norm_set_stats(self._h, abi.ptr(arrs[0]), abi.ptr(arrs[1]), abi.ptr(arrs[2]), abi.ptr(ret),
-                                          self._stream()), "pgx_norm_set_stats", self.lib)
+        self._call("set_stats", self._h, abi.ptr(arrs[0]), abi.ptr(arrs[1]), abi.ptr(arrs[2]), abi.ptr(ret),
+                   self._stream())
 
     # ------------------------------------------- array-level step (tests, tools)
     def alloc_outputs(self) -> Dict[str, "torch.Tensor"]:
@@ -169,10 +143,6 @@ class Normalizer:
                 "desired_goal": torch.zeros((n, 3), **kw), "reward": torch.zeros((n,), **kw),
                 "terminal_obs": torch.zeros((n, od), **kw), "terminal_ag": torch.zeros((n, 3), **kw),
                 "terminal_dg": torch.zeros((n, 3), **kw)}
-
-    def _dev(self, x, shape, dtype):
-        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-        return t.to(device=self.device, dtype=dtype).reshape(shape).contiguous()
 
     def step_arrays(self, obs, achieved_goal, desired_goal, reward, terminated, truncated, terminal_obs=None,
                     terminal_ag=None, terminal_dg=None, out: Optional[Dict[str, "torch.Tensor"]] = None):

@@ -24,6 +24,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import abi
+from ._native import check
 from ._policy import Policy, torch
 
 SETS = ("online", "target")
@@ -104,13 +105,13 @@ class QuantileCritic(Policy):
     def _push(self) -> None:
         for s in self._loading:
             w = self._set_struct(s)
-            self._lib_call("set_weights", self._h, abi.QC_SETS[s], C.byref(w), self._stream())
+            self._call("set_weights", self._h, abi.QC_SETS[s], C.byref(w), self._stream())
 
     def _pull_target(self) -> None:
         """The handle's plain copy of the target set into the tensors here (after a Polyak step or a sync)."""
         if self._h is not None and self._stale:
             w = self._set_struct("target")
-            self._lib_call("get_weights", self._h, abi.QC_TARGET, C.byref(w), self._stream())
+            self._call("get_weights", self._h, abi.QC_TARGET, C.byref(w), self._stream())
             self._stale = False
 
     # ----------------------------------------------------------- parameters
@@ -203,7 +204,8 @@ class QuantileCritic(Policy):
         io, B, keep = self._io(obs, actions)
         q = self._out(out, B, self.n_pool)
         io.out = q.data_ptr()
-        self._lib_call("forward", self._h, abi.QC_TARGET if target else abi.QC_ONLINE, C.byref(io), B, self._stream())
+        check(self.lib.pgx_qc_forward(self._h, abi.QC_TARGET if target else abi.QC_ONLINE, C.byref(io), B, self._stream()),
+              "pgx_qc_forward", self.lib)
         self._keep = keep + [q]
         return q.view(B, self.n_critics, self.n_quantiles) if out is None else out
 
@@ -231,7 +233,7 @@ class QuantileCritic(Policy):
             e.data_ptr(), t.data_ptr()
         if quantiles is not None:
             io.quantiles_out = self._out(quantiles, B, self.n_pool).data_ptr()
-        self._lib_call("target", self._h, C.byref(io), B, self.n_target, self._stream())
+        self._call("target", self._h, C.byref(io), B, self.n_target, self._stream())
         self._keep = keep + [r, d, lp, e, t, quantiles]
         return t
 
@@ -249,14 +251,14 @@ class QuantileCritic(Policy):
         copies, by the rule of include/pgx.h (``t = fmaf(tau, p, t * (1 - tau))``), then the target's
         packing, on the current stream: the next target launch, eager or a replay, uses it.  Device only."""
         self._need_device()
-        self._lib_call("polyak", self._h, C.c_double(float(tau)), self._stream())
+        self._call("polyak", self._h, C.c_double(float(tau)), self._stream())
         self._stale = True
 
     def sync_target(self) -> None:
         """``critic_target.load_state_dict(critic.state_dict())``: the online set into the target, bit for
         bit, one launch on the current stream.  Device only."""
         self._need_device()
-        self._lib_call("sync_target", self._h, self._stream())
+        self._call("sync_target", self._h, self._stream())
         self._stale = True
 
     # ------------------------------------------------------------ host models
@@ -286,7 +288,7 @@ class QuantileCritic(Policy):
         w, keep_w = self._host_set("target" if target else "online")
         out = np.zeros((n, self.n_critics, self.n_quantiles), np.float32)
         io.out = abi.ptr(out)
-        self._lib_call("forward_host", C.byref(self._cfg), C.byref(w), C.byref(io), n)
+        self._call("forward_host", C.byref(self._cfg), C.byref(w), C.byref(io), n)
         return out
 
     def td_target_host(self, next_obs: Dict[str, Any], next_actions, next_log_prob, rewards, dones, ent_coef,
@@ -306,5 +308,5 @@ class QuantileCritic(Policy):
         io.reward, io.done, io.next_log_prob, io.ent_coef = abi.ptr(r), abi.ptr(d), abi.ptr(lp), abi.ptr(e)
         io.reward_stride = io.done_stride = 1
         io.out, io.quantiles_out = abi.ptr(out), abi.ptr(pool)
-        self._lib_call("target_host", C.byref(self._cfg), C.byref(w), C.byref(io), n, nt)
+        self._call("target_host", C.byref(self._cfg), C.byref(w), C.byref(io), n, nt)
         return (out, pool) if return_quantiles else out

@@ -20,16 +20,10 @@ from typing import Any, Callable, Dict, Iterator, List, NamedTuple, Optional
 import numpy as np
 
 from . import abi
+from ._handle import OBS_KEYS, Handle, _view, resolve_dims, torch
 from ._native import PgxError, check, load
 from .monitor import VecMonitor
 from .normalize import VecNormalize
-
-try:
-    import torch
-except ImportError:  # pragma: no cover
-    torch = None
-
-OBS_KEYS = ("observation", "achieved_goal", "desired_goal")
 
 
 class RolloutBufferSamples(NamedTuple):
@@ -68,7 +62,7 @@ def terminal_observation(venv) -> Dict[str, "torch.Tensor"]:
             "desired_goal": pick("terminal_dg")}
 
 
-class RolloutBuffer:
+class RolloutBuffer(Handle):
     """SB3 ``DictRolloutBuffer`` of ``buffer_size`` steps x ``n_envs`` envs on the device.
 
     ``env`` may be a ``PandaVecEnv`` or a wrapper of one (``n_envs`` and the dims are read from it).
@@ -76,38 +70,24 @@ class RolloutBuffer:
     ``capture_steps``), then ``compute_returns_and_advantage`` and ``get``; ``reset`` starts the
     next rollout and keeps the carry, as SB3's ``rollout_buffer.reset()`` keeps ``_last_obs``."""
 
+    _PREFIX = "pgx_rollout"
+
     def __init__(self, buffer_size: int, observation_space: Any = None, action_space: Any = None,
                  device: Any = "cuda:0", gae_lambda: float = 1.0, gamma: float = 0.99, n_envs: int = 1, env: Any = None,
                  seed: int = 0, obs_dim: Optional[int] = None, action_dim: Optional[int] = None):
-        if torch is None:
-            raise PgxError("RolloutBuffer needs torch for device buffers")
+        self._need_torch()
         self.lib = load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise PgxError("RolloutBuffer lives on a HIP device only (no CPU fallback)")
-        if env is not None:
-            n_envs = env.num_envs
-            obs_dim = env.obs_dim if obs_dim is None else obs_dim
-            action_dim = env.action_dim if action_dim is None else action_dim
-        if observation_space is not None and obs_dim is None:
-            obs_dim = int(np.prod(observation_space["observation"].shape))
-        if action_space is not None and action_dim is None:
-            action_dim = int(np.prod(action_space.shape))
-        if obs_dim is None or action_dim is None:
-            raise ValueError("obs_dim/action_dim: pass env, the spaces, or the dims")
-        self.buffer_size, self.n_envs = int(buffer_size), int(n_envs)   # SB3 RolloutBuffer: buffer_size = n_steps
-        self.obs_dim, self.action_dim = int(obs_dim), int(action_dim)
+        self._on_device(device)
+        self.n_envs, self.obs_dim, self.action_dim = resolve_dims(env, observation_space, action_space, n_envs, obs_dim,
+                                                                  action_dim)
+        self.buffer_size = int(buffer_size)   # SB3 RolloutBuffer: buffer_size = n_steps
         self.gamma, self.gae_lambda, self.seed = float(gamma), float(gae_lambda), int(seed)
         self.env = env
         cfg = abi.PgxRolloutConfig(self.n_envs, self.buffer_size, self.obs_dim, self.action_dim, self.gamma,
                                    self.gae_lambda, self.seed & 0xFFFFFFFFFFFFFFFF)
         self._cfg = cfg
         self._fields, self.row_dim = abi.rollout_row_fields(self.obs_dim, self.action_dim)
-        h = C.c_void_p()
-        torch.cuda.set_device(self.device)
-        check(self.lib.pgx_rollout_create(C.byref(cfg), self.device.index or 0, C.byref(h)), "pgx_rollout_create",
-              self.lib)
-        self._h = h
+        self._create(cfg)
         self.row_stride = self.lib.pgx_rollout_row_stride(C.byref(cfg))
         if self.lib.pgx_rollout_row_dim(C.byref(cfg)) != self.row_dim:
             raise PgxError("libpgx batch row layout differs from abi.rollout_row_fields")
@@ -117,35 +97,12 @@ class RolloutBuffer:
         self._keep: List[Any] = []
 
     # ------------------------------------------------------------ plumbing
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            torch.cuda.synchronize(self.device)
-            self.lib.pgx_rollout_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _dev(self, x, shape) -> "torch.Tensor":
-        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-        return t.to(device=self.device, dtype=torch.float32).reshape(shape).contiguous()
-
     def _flag(self, x) -> Optional["torch.Tensor"]:
-        if x is None:
-            return None
-        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-        return t.to(device=self.device, dtype=torch.uint8).reshape((self.n_envs,)).contiguous()
+        return None if x is None else self._dev(x, (self.n_envs,), torch.uint8)
 
     def _state(self, clear: bool = False):
         pos, err = C.c_int32(0), C.c_uint32(0)
-        check(self.lib.pgx_rollout_state(self._h, C.byref(pos), C.byref(err), 1 if clear else 0, self._stream()),
-              "pgx_rollout_state", self.lib)
+        self._call("state", self._h, C.byref(pos), C.byref(err), 1 if clear else 0, self._stream())
         return int(pos.value), int(err.value)
 
     # ---------------------------------------------------------------- state
@@ -166,11 +123,8 @@ class RolloutBuffer:
         """Raise what the kernels flagged in the sticky device word and clear it (one sync)."""
         self._raise(self._state(clear=True)[1])
 
-    @staticmethod
-    def _raise(err: int) -> None:
-        if err:
-            names = [msg for bit, msg in abi.ROLLOUT_ERRORS.items() if err & bit]
-            raise PgxError("; ".join(names) if names else f"rollout device error flags 0x{err:x}")
+    def _raise(self, err: int) -> None:
+        self._raise_flags(err, abi.ROLLOUT_ERRORS, "rollout")
 
     def arrays(self) -> Dict[str, "torch.Tensor"]:
         """Device views of every stored plane: ``observation`` [T, N, obs_dim], ``achieved_goal`` /
@@ -178,10 +132,8 @@ class RolloutBuffer:
         ``episode_start``, ``value``, ``log_prob``, ``advantage``, ``return`` [T, N], and the carry
         ``last_observation`` [N, obs_dim], ``last_achieved_goal`` / ``last_desired_goal`` [N, 3],
         ``last_episode_start`` [N]."""
-        from .envs import _view
-
         v = abi.PgxRolloutViews()
-        check(self.lib.pgx_rollout_arrays(self._h, C.byref(v)), "pgx_rollout_arrays", self.lib)
+        self._call("arrays", self._h, C.byref(v))
         T, N, od, ad, R, f = self.buffer_size, self.n_envs, self.obs_dim, self.action_dim, int(v.record_stride), \
             torch.float32
         rec = _view(v.records, (T, N, R), f, self.device)
@@ -199,7 +151,7 @@ class RolloutBuffer:
     # -------------------------------------------------------------- collect
     def reset(self) -> None:
         """SB3 ``RolloutBuffer.reset``: ``pos = 0`` (one launch); the carry stays."""
-        check(self.lib.pgx_rollout_reset(self._h, self._stream()), "pgx_rollout_reset", self.lib)
+        self._call("reset", self._h, self._stream())
 
     def set_last(self, obs: Dict[str, Any], episode_starts: Any = None) -> None:
         """The carry, SB3's ``_last_obs`` / ``_last_episode_starts``: the observation dict of
@@ -207,8 +159,7 @@ class RolloutBuffer:
         N = self.n_envs
         t = [self._dev(obs["observation"], (N, self.obs_dim)), self._dev(obs["achieved_goal"], (N, 3)),
              self._dev(obs["desired_goal"], (N, 3)), None if episode_starts is None else self._dev(episode_starts, (N,))]
-        check(self.lib.pgx_rollout_set_last(self._h, *[None if x is None else C.c_void_p(x.data_ptr()) for x in t],
-                                            self._stream()), "pgx_rollout_set_last", self.lib)
+        self._call("set_last", self._h, *[None if x is None else C.c_void_p(x.data_ptr()) for x in t], self._stream())
         self._keep_last = t   # read by the queued launch
 
     def _launch_add(self, action, reward, value, log_prob, terminal_value, obs, terminated, truncated) -> None:
@@ -294,9 +245,8 @@ class RolloutBuffer:
         """The GAE launch alone: no sync, no look at the error word (a captured or timed loop)."""
         lv = self._dev(last_values, (self.n_envs,))
         dn = None if dones is None else self._dev(dones, (self.n_envs,))
-        check(self.lib.pgx_rollout_compute_returns_and_advantage(
-            self._h, C.c_void_p(lv.data_ptr()), None if dn is None else C.c_void_p(dn.data_ptr()), self._stream()),
-            "pgx_rollout_compute_returns_and_advantage", self.lib)
+        self._call("compute_returns_and_advantage", self._h, C.c_void_p(lv.data_ptr()),
+                   None if dn is None else C.c_void_p(dn.data_ptr()), self._stream())
         self._keep_gae = (lv, dn)
 
     def permutation(self, epoch: Optional[int] = None) -> "torch.Tensor":
@@ -304,9 +254,8 @@ class RolloutBuffer:
         flat indices ``env * n_steps + step`` in the buffer's own tensor, one launch."""
         if epoch is None:
             epoch, self.epoch = self.epoch, self.epoch + 1
-        check(self.lib.pgx_rollout_permutation(self._h, C.c_uint64(int(epoch) & 0xFFFFFFFFFFFFFFFF),
-                                               C.c_void_p(self._perm.data_ptr()), self._stream()),
-              "pgx_rollout_permutation", self.lib)
+        self._call("permutation", self._h, C.c_uint64(int(epoch) & 0xFFFFFFFFFFFFFFFF),
+                   C.c_void_p(self._perm.data_ptr()), self._stream())
         return self._perm
 
     def alloc_batch(self, batch_size: int) -> Dict[str, "torch.Tensor"]:

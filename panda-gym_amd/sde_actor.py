@@ -23,6 +23,7 @@ from typing import Any, Callable, Dict, Optional, Sequence
 import numpy as np
 
 from . import abi
+from ._native import check
 from ._policy import Policy, torch
 
 
@@ -82,7 +83,7 @@ class SdeActor(Policy):
 
     def _push(self) -> None:
         w = self._weights_struct([t.data_ptr() for t in self._w], [t.data_ptr() for t in self._b], self._log_std.data_ptr())
-        self._lib_call("set_weights", self._h, C.byref(w), self._stream())
+        self._call("set_weights", self._h, C.byref(w), self._stream())
 
     # ----------------------------------------------------------- parameters
     def _slots(self):
@@ -101,7 +102,7 @@ class SdeActor(Policy):
         """``exp(log_std)`` [H, A] as the handle holds it (a copy)."""
         self._need_device()
         out = torch.empty_like(self._log_std)
-        self._lib_call("get_std", self._h, C.c_void_p(out.data_ptr()), self._stream())
+        self._call("get_std", self._h, C.c_void_p(out.data_ptr()), self._stream())
         return out
 
     # ----------------------------------------------------------------- noise
@@ -122,7 +123,7 @@ class SdeActor(Policy):
         self._need_device()
         d = self._debug
         e, p = (None, None) if d is None else (C.c_void_p(d["eps"].data_ptr()), C.c_void_p(d["philox"].data_ptr()))
-        self._lib_call("reset_noise", self._h, e, p, self._stream())
+        self._call("reset_noise", self._h, e, p, self._stream())
 
     noise_generation = property(Policy._get_word, Policy._set_word, doc="""The device word that keys the matrix draw
         and counts the resamples (this synchronises).  Setting it back reproduces the draws.""")
@@ -132,14 +133,14 @@ class SdeActor(Policy):
         """The matrices [N, H, A] in SB3's layout (a copy; the handle keeps a layout of its own)."""
         self._need_device()
         out = torch.empty((self.n_envs, self.latent_dim, self.action_dim), dtype=torch.float32, device=self.device)
-        self._lib_call("get_matrices", self._h, C.c_void_p(out.data_ptr()), self._stream())
+        self._call("get_matrices", self._h, C.c_void_p(out.data_ptr()), self._stream())
         return out
 
     @exploration_matrices.setter
     def exploration_matrices(self, value: Any) -> None:
         self._need_device()
         t = self._dev(value, (self.n_envs, self.latent_dim, self.action_dim))
-        self._lib_call("set_matrices", self._h, C.c_void_p(t.data_ptr()), self._stream())
+        self._call("set_matrices", self._h, C.c_void_p(t.data_ptr()), self._stream())
         self._keep_m = t   # alive until the stream has consumed it
 
     # --------------------------------------------------------------- forward
@@ -148,7 +149,8 @@ class SdeActor(Policy):
         p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         io = abi.PgxSdeActorIo(p(obs["observation"]), p(obs["achieved_goal"]), p(obs["desired_goal"]), p(self.actions),
                                *([None] * 3 if d is None else [p(d[k]) for k in ("mean", "latent", "noise")]))
-        self._lib_call("forward", self._h, C.byref(io), 1 if deterministic else 0, self._stream())
+        check(self.lib.pgx_sde_actor_forward(self._h, C.byref(io), 1 if deterministic else 0, self._stream()),
+              "pgx_sde_actor_forward", self.lib)
 
     def __call__(self, obs: Dict[str, Any], deterministic: bool = False) -> "torch.Tensor":
         """Actions [N, A] for the observation dict ``obs`` (what ``step_tensors`` / ``reset_tensors`` of an
@@ -174,7 +176,7 @@ class SdeActor(Policy):
         ls = np.ascontiguousarray(self._log_std.cpu().numpy())
         w = self._weights_struct([x.ctypes.data for x in ws], [x.ctypes.data for x in bs], ls.ctypes.data)
         mean, latent, noise = np.zeros((n, A), np.float32), np.zeros((n, H), np.float32), np.zeros((n, A), np.float32)
-        self._lib_call("forward_host", C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
+        self._call("forward_host", C.byref(self._cfg), C.byref(w), abi.ptr(o["observation"]),
                        abi.ptr(o["achieved_goal"]), abi.ptr(o["desired_goal"]), abi.ptr(m), n, abi.ptr(mean),
                        abi.ptr(latent), abi.ptr(noise))
         return mean, latent, noise

@@ -6,18 +6,16 @@ test_actor_abi.py (libm's fmaf through ctypes, ascending k, the accumulator star
 up to 16), bit for bit, for unequal trunk depths."""
 import ctypes as C
 import inspect
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import panda_gym_amd as pg
+from abi_checks import assert_exported, header_layout
 from panda_gym_amd import _native, abi
 from test_actor_abi import bits, chain, features, random_obs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 AC_EXPORTS = ["pgx_ac_create", "pgx_ac_destroy", "pgx_ac_set_weights", "pgx_ac_forward", "pgx_ac_values",
               "pgx_ac_state", "pgx_ac_set_state", "pgx_ac_forward_host"]
@@ -58,24 +56,9 @@ def restated_forward(ac, sd, obs):
 
 
 # ---------------------------------------------------------------- the C-ABI
-def test_struct_layout_matches_header(tmp_path):
+def test_struct_layout_matches_header():
     structs = {"pgx_ac_config": abi.PgxAcConfig, "pgx_ac_weights": abi.PgxAcWeights, "pgx_ac_io": abi.PgxAcIo}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT}/include/pgx.h"', "int main(void){"]
-    for s, cls in structs.items():
-        lines.append(f'printf("{s} %zu\\n", sizeof({s}));')
-        for f, _ in cls._fields_:
-            lines.append(f'printf("{s}.{f} %zu\\n", offsetof({s}, {f}));')
-    lines.append('printf("tag %u\\n", PGX_AC_PHILOX_TAG);')
-    lines.append("return 0;}")
-    src, exe = tmp_path / "lay.c", tmp_path / "lay"
-    src.write_text("\n".join(lines))
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-o", str(exe), str(src)], check=True)
-    text = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout
-    out = dict(l.split(" ", 1) for l in text.split("\n") if l)
-    for s, cls in structs.items():
-        assert int(out[s]) == C.sizeof(cls), s
-        for f, _ in cls._fields_:
-            assert int(out[f"{s}.{f}"]) == getattr(cls, f).offset, (s, f)
+    out = header_layout(structs, ['printf("tag %u\\n", PGX_AC_PHILOX_TAG);'])
     assert int(out["tag"]) == abi.AC_PHILOX_TAG
     assert abi.AC_PHILOX_TAG != abi.ACTOR_PHILOX_TAG
     # no dimension pair of one stream meets one of the other
@@ -83,15 +66,7 @@ def test_struct_layout_matches_header(tmp_path):
 
 
 def test_library_exports_the_entry_points():
-    lib = _native.load()
-    for name in AC_EXPORTS:
-        assert hasattr(lib, name), name
-        assert name in _native.EXPORTS, name
-    rt = os.path.join(ROOT, "panda-gym_amd", "libpgx_rtmodel.so")
-    assert os.path.exists(rt), "build() makes the runtime-model library too"
-    rtlib = C.CDLL(rt)
-    for name in AC_EXPORTS:
-        assert hasattr(rtlib, name), name
+    assert_exported(AC_EXPORTS)
 
 
 def good_config():

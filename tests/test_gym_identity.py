@@ -87,7 +87,11 @@ def test_stand_ins_without_gymnasium_and_sb3():
     from panda_gym_amd import envs
     if envs._gym is not None or envs._sb3_vec is not None:
         pytest.skip("gymnasium / stable-baselines3 are installed")
-    assert envs.PandaVecEnv.__bases__ == (object,) and envs.PandaEnv.__bases__ == (object,)
+    from panda_gym_amd._handle import Handle
+
+    # (the handle base, then the stand-in for SB3's VecEnv)
+    assert envs.PandaVecEnv.__bases__ == (Handle, object) and envs.PandaEnv.__bases__ == (object,)
+    assert Handle.__bases__ == (object,)
     obs, act = envs.make_spaces(18, 3)
     assert isinstance(obs, envs.DictSpace) and isinstance(act, envs.Box)
     assert obs["observation"].shape == (18,) and act.shape == (3,) and act.dtype == "float32"

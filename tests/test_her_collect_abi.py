@@ -3,14 +3,13 @@
 exported entry points, the Python surface, and RefCollect, the numpy restatement the GPU tests compare
 against, written from the rules of include/pgx.h: carry -> transition -> oracle.her.HerOracle.add, plus
 SB3's truncate_last_trajectory.  It is pinned on a trace small enough to follow by hand."""
-import ctypes as C
 import inspect
 import os
-import subprocess
 
 import numpy as np
 
 from oracle import her as H
+from abi_checks import assert_exported, header_layout
 from panda_gym_amd import _native, abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -95,37 +94,17 @@ class RefCollect:
 
 
 # ---------------------------------------------------------------- the C-ABI
-def test_struct_layout_matches_header(tmp_path):
+def test_struct_layout_matches_header():
     """ctypes mirrors of pgx_replay_step / pgx_replay_views == the header's sizeof / offsetof (gcc, as C)."""
     structs = {"pgx_replay_step": abi.PgxReplayStep, "pgx_replay_views": abi.PgxReplayViews}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT}/include/pgx.h"', "int main(void){"]
-    for s, cls in structs.items():
-        lines.append(f'printf("{s} %zu\\n", sizeof({s}));')
-        for f, _ in cls._fields_:
-            lines.append(f'printf("{s}.{f} %zu\\n", offsetof({s}, {f}));')
-    lines.append("return 0;}")
-    src, exe = tmp_path / "lay.c", tmp_path / "lay"
-    src.write_text("\n".join(lines))
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-o", str(exe), str(src)], check=True)
-    out = dict(l.rsplit(" ", 1) for l in subprocess.run([str(exe)], capture_output=True, text=True,
-                                                          check=True).stdout.split("\n") if l)
-    for s, cls in structs.items():
-        assert int(out[s]) == C.sizeof(cls), s
-        for f, _ in cls._fields_:
-            assert int(out[f"{s}.{f}"]) == getattr(cls, f).offset, (s, f)
+    header_layout(structs)
     hdr = open(os.path.join(ROOT, "include", "pgx.h")).read()
     assert f"#define PGX_REPLAY_ERR_NO_CARRY {ERR_NO_CARRY}" in hdr
     assert abi.REPLAY_ERR_NO_CARRY == ERR_NO_CARRY and ERR_NO_CARRY in abi.REPLAY_ERRORS
 
 
 def test_library_exports_the_entry_points():
-    lib = _native.load()
-    for name in COLLECT_EXPORTS:
-        assert hasattr(lib, name), name
-        assert name in _native.EXPORTS, name
-    rtlib = C.CDLL(os.path.join(ROOT, "panda-gym_amd", "libpgx_rtmodel.so"))
-    for name in COLLECT_EXPORTS:
-        assert hasattr(rtlib, name), name
+    assert_exported(COLLECT_EXPORTS)
 
 
 def test_null_handles_are_rejected_without_a_device():

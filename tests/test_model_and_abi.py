@@ -3,13 +3,12 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 
+from abi_checks import header_layout
 from panda_gym_amd import abi
 from panda_gym_amd.model import bullet_quicksort_equal_keys, forward_kinematics, load_model
 
@@ -68,6 +67,42 @@ def test_libpgx_exports_every_declared_symbol():
         assert hasattr(lib, name), name
     assert set(decl) == set(_native.EXPORTS)
     assert lib.pgx_version().startswith(b"pgx")
+
+
+def _declarations():
+    """(return type, name, [parameter declarations]) of every function include/pgx.h declares."""
+    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, "include", "pgx.h")).read(), flags=re.S)
+    out = []
+    for ret, name, params in re.findall(r"^\s*((?:const\s+)?[a-z_0-9]+\*?)\s+\*?(pgx_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", hdr,
+                                        re.M):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        out.append((" ".join(ret.split()), name, [] if params == ["void"] else params))
+    return out
+
+
+def test_signature_table_matches_the_header():
+    """_native.SIGNATURES against the declarations of include/pgx.h, without a library: the number of
+    parameters; a scalar parameter has the ctypes type of its C type; a pointer or a handle has c_void_p
+    or a POINTER(...); the restype is None for void, c_char_p for const char*, c_int64 for int64_t and
+    ctypes' default for int."""
+    from panda_gym_amd import _native
+
+    scalars = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double}
+    restypes = {"void": None, "const char*": C.c_char_p, "int64_t": C.c_int64, "int": _native.INT}
+    decl = _declarations()
+    assert sorted(d[1] for d in decl) == _declared_functions()   # (every declaration was parsed)
+    assert set(_native.SIGNATURES) == {d[1] for d in decl} and _native.EXPORTS == list(_native.SIGNATURES)
+    for ret, name, params in decl:
+        argtypes, restype = _native.SIGNATURES[name]
+        assert len(argtypes) == len(params), name
+        for a, p in zip(argtypes, params):
+            ctype = [w for w in p.split()[:-1] if w != "const"]
+            if "*" in p or ctype[-1].endswith("_handle"):
+                assert a is C.c_void_p or issubclass(a, C._Pointer), (name, p)
+            else:
+                assert ctype[-1] in scalars and a is scalars[ctype[-1]], (name, p)
+                assert C.sizeof(a) == {"int": 4, "int32_t": 4}.get(ctype[-1], 8), (name, p)
+        assert ret in restypes and restype is restypes[ret], (name, ret)
 
 
 def test_host_only_calls_without_gpu():
@@ -162,33 +197,9 @@ def test_constants_match_header():
     assert abi.AO_OBSTACLES == define("PGX_AO_OBSTACLES") and abi.MAX_CAPSULES == define("PGX_MAX_CAPSULES")
 
 
-def test_struct_layout_matches_c(tmp_path):
-    """ctypes mirror == C layout of include/pgx.h (sizeof/offsetof via gcc)."""
-    src = tmp_path / "lay.c"
-    fields = {"pgx_model": ["n_rows", "jpos", "jrot", "mass", "lower", "upper"],
-              "pgx_sim_params": ["dt", "ik_max_angle", "n_substeps", "flags"],
-              "pgx_config": ["no_auto_reset", "seed", "base_pos", "joint_forces", "model", "params",
-                             "terminate_on_success", "collision_reward", "ao_ee_neutral"],
-              "pgx_step_out": ["terminal_achieved_goal", "terminal_desired_goal"],
-              "pgx_replay_config": ["reward_type", "distance_threshold", "her_ratio", "seed"],
-              "pgx_transition": ["next_obs", "done", "timeout"],
-              "pgx_replay_batch": ["rows", "env", "goal_slot"], "pgx_state_view": ["episode", "errors", "robot_points"]}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT}/include/pgx.h"', "int main(){"]
-    for s, fs in fields.items():
-        lines.append(f'printf("{s} %zu\\n", sizeof({s}));')
-        for f in fs:
-            lines.append(f'printf("{s}.{f} %zu\\n", offsetof({s}, {f}));')
-    lines.append("return 0;}")
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "lay"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    out = dict(l.rsplit(" ", 1) for l in subprocess.run([str(exe)], capture_output=True, text=True,
-                                                          check=True).stdout.split("\n") if l)
-    py = {"pgx_model": abi.PgxModel, "pgx_sim_params": abi.PgxSimParams, "pgx_config": abi.PgxConfig,
-          "pgx_step_out": abi.PgxStepOut, "pgx_state_view": abi.PgxStateView,
-          "pgx_replay_config": abi.PgxReplayConfig, "pgx_transition": abi.PgxTransition,
-          "pgx_replay_batch": abi.PgxReplayBatch}
-    for s, cls in py.items():
-        assert int(out[s]) == C.sizeof(cls), s
-        for f in fields[s]:
-            assert int(out[f"{s}.{f}"]) == getattr(cls, f).offset, (s, f)
+def test_struct_layout_matches_c():
+    """ctypes mirror == C layout of include/pgx.h (sizeof, and offsetof of every field, via gcc)."""
+    header_layout({"pgx_model": abi.PgxModel, "pgx_sim_params": abi.PgxSimParams, "pgx_config": abi.PgxConfig,
+                   "pgx_step_out": abi.PgxStepOut, "pgx_state_view": abi.PgxStateView,
+                   "pgx_replay_config": abi.PgxReplayConfig, "pgx_transition": abi.PgxTransition,
+                   "pgx_replay_batch": abi.PgxReplayBatch})

@@ -3,11 +3,11 @@ header's layout through gcc, the exported entry points, pgx_norm_create's argume
 before any device call), and the numpy restatement of RunningMeanStd the GPU tests compare against."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_checks import assert_exported, header_layout
 from panda_gym_amd import _native, abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,24 +34,10 @@ class RunningMeanStd:
         self.mean, self.var, self.count = new_mean, m2 / tot, tot
 
 
-def test_struct_layout_matches_header(tmp_path):
+def test_struct_layout_matches_header():
     """ctypes mirrors of pgx_norm_config / pgx_norm_io == the header's sizeof / offsetof (gcc, as C)."""
     structs = {"pgx_norm_config": abi.PgxNormConfig, "pgx_norm_io": abi.PgxNormIo}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT}/include/pgx.h"', "int main(void){"]
-    for s, cls in structs.items():
-        lines.append(f'printf("{s} %zu\\n", sizeof({s}));')
-        for f, _ in cls._fields_:
-            lines.append(f'printf("{s}.{f} %zu\\n", offsetof({s}, {f}));')
-    lines.append("return 0;}")
-    src, exe = tmp_path / "lay.c", tmp_path / "lay"
-    src.write_text("\n".join(lines))
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-o", str(exe), str(src)], check=True)
-    out = dict(l.rsplit(" ", 1) for l in subprocess.run([str(exe)], capture_output=True, text=True,
-                                                          check=True).stdout.split("\n") if l)
-    for s, cls in structs.items():
-        assert int(out[s]) == C.sizeof(cls), s
-        for f, _ in cls._fields_:
-            assert int(out[f"{s}.{f}"]) == getattr(cls, f).offset, (s, f)
+    header_layout(structs)
     hdr = open(os.path.join(ROOT, "include", "pgx.h")).read()
     assert "#define PGX_NORM_KEY_ALL 7" in hdr and abi.NORM_KEY_ALL == 7
     assert "#define PGX_NORM_REWARD 3" in hdr and abi.NORM_REWARD == 3
@@ -59,15 +45,7 @@ def test_struct_layout_matches_header(tmp_path):
 
 
 def test_library_exports_the_entry_points():
-    lib = _native.load()
-    for name in NORM_EXPORTS:
-        assert hasattr(lib, name), name
-        assert name in _native.EXPORTS, name
-    rt = os.path.join(ROOT, "panda-gym_amd", "libpgx_rtmodel.so")
-    assert os.path.exists(rt), "build() makes the runtime-model library too"
-    rtlib = C.CDLL(rt)
-    for name in NORM_EXPORTS:
-        assert hasattr(rtlib, name), name
+    assert_exported(NORM_EXPORTS)
 
 
 @pytest.mark.parametrize("field,value", [("n_envs", 0), ("n_envs", -3), ("obs_dim", 0), ("obs_dim", -1),

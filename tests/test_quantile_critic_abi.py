@@ -9,17 +9,15 @@ operations -- both bit for bit.  The Polyak rule has no host path: it is pinned 
 (test_gpu_quantile_critic.py)."""
 import ctypes as C
 import inspect
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import panda_gym_amd as pg
+from abi_checks import assert_exported, header_layout
 from panda_gym_amd import _native, abi
 from test_actor_abi import bits, chain, random_obs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 QC_EXPORTS = ["pgx_qc_create", "pgx_qc_destroy", "pgx_qc_set_weights", "pgx_qc_get_weights", "pgx_qc_forward",
               "pgx_qc_target", "pgx_qc_polyak", "pgx_qc_sync_target", "pgx_qc_forward_host", "pgx_qc_target_host"]
@@ -111,25 +109,10 @@ def target_inputs(rng, n):
 
 
 # ---------------------------------------------------------------- the C-ABI
-def test_struct_layout_matches_header(tmp_path):
+def test_struct_layout_matches_header():
     structs = {"pgx_qc_config": abi.PgxQcConfig, "pgx_qc_weights": abi.PgxQcWeights, "pgx_qc_io": abi.PgxQcIo}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT}/include/pgx.h"', "int main(void){"]
-    for s, cls in structs.items():
-        lines.append(f'printf("{s} %zu\\n", sizeof({s}));')
-        for f, _ in cls._fields_:
-            lines.append(f'printf("{s}.{f} %zu\\n", offsetof({s}, {f}));')
-    lines.append('printf("consts %d %d %d %d %d\\n", PGX_QC_ONLINE, PGX_QC_TARGET, PGX_QC_MAX_CRITICS, '
-                 'PGX_QC_MAX_QUANTILES, PGX_QC_MAX_POOL);')
-    lines.append("return 0;}")
-    src, exe = tmp_path / "lay.c", tmp_path / "lay"
-    src.write_text("\n".join(lines))
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-o", str(exe), str(src)], check=True)
-    text = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout
-    out = dict(l.split(" ", 1) for l in text.split("\n") if l)
-    for s, cls in structs.items():
-        assert int(out[s]) == C.sizeof(cls), s
-        for f, _ in cls._fields_:
-            assert int(out[f"{s}.{f}"]) == getattr(cls, f).offset, (s, f)
+    out = header_layout(structs, ['printf("consts %d %d %d %d %d\\n", PGX_QC_ONLINE, PGX_QC_TARGET, PGX_QC_MAX_CRITICS, '
+                 'PGX_QC_MAX_QUANTILES, PGX_QC_MAX_POOL);'])
     assert out["consts"] == f"{abi.QC_ONLINE} {abi.QC_TARGET} {abi.QC_MAX_CRITICS} {abi.QC_MAX_QUANTILES} {abi.QC_MAX_POOL}"
     assert abi.QC_SETS == {"online": 0, "target": 1}
     # weight[c][l]: critic-major, four Linears each
@@ -139,15 +122,7 @@ def test_struct_layout_matches_header(tmp_path):
 
 
 def test_library_exports_the_entry_points():
-    lib = _native.load()
-    for name in QC_EXPORTS:
-        assert hasattr(lib, name), name
-        assert name in _native.EXPORTS, name
-    rt = os.path.join(ROOT, "panda-gym_amd", "libpgx_rtmodel.so")
-    assert os.path.exists(rt), "build() makes the runtime-model library too"
-    rtlib = C.CDLL(rt)
-    for name in QC_EXPORTS:
-        assert hasattr(rtlib, name), name
+    assert_exported(QC_EXPORTS)
 
 
 def good_config(obs_dim=6, hidden0=16, n_critics=2, n_quantiles=5):

@@ -6,17 +6,15 @@ fmaf through ctypes; the trunk and mu as the Actor's chain (bias first, k ascend
 the noise as ONE chain from +0 over exactly H terms, h ascending -- bit for bit."""
 import ctypes as C
 import inspect
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import panda_gym_amd as pg
+from abi_checks import assert_exported, header_layout
 from panda_gym_amd import _native, abi
 from test_actor_abi import bits, chain, features, fmaf, random_obs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 SDE_EXPORTS = ["pgx_sde_actor_create", "pgx_sde_actor_destroy", "pgx_sde_actor_set_weights", "pgx_sde_actor_reset_noise",
                "pgx_sde_actor_forward", "pgx_sde_actor_state", "pgx_sde_actor_set_state", "pgx_sde_actor_get_matrices",
@@ -71,25 +69,10 @@ def restated_forward(actor, sd, obs, matrices):
 
 
 # ---------------------------------------------------------------- the C-ABI
-def test_struct_layout_matches_header(tmp_path):
+def test_struct_layout_matches_header():
     structs = {"pgx_sde_actor_config": abi.PgxSdeActorConfig, "pgx_sde_actor_weights": abi.PgxSdeActorWeights,
                "pgx_sde_actor_io": abi.PgxSdeActorIo}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT}/include/pgx.h"', "int main(void){"]
-    for s, cls in structs.items():
-        lines.append(f'printf("{s} %zu\\n", sizeof({s}));')
-        for f, _ in cls._fields_:
-            lines.append(f'printf("{s}.{f} %zu\\n", offsetof({s}, {f}));')
-    lines.append('printf("tag %u\\n", PGX_SDE_PHILOX_TAG);')
-    lines.append("return 0;}")
-    src, exe = tmp_path / "lay.c", tmp_path / "lay"
-    src.write_text("\n".join(lines))
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-o", str(exe), str(src)], check=True)
-    text = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout
-    out = dict(l.split(" ", 1) for l in text.split("\n") if l)
-    for s, cls in structs.items():
-        assert int(out[s]) == C.sizeof(cls), s
-        for f, _ in cls._fields_:
-            assert int(out[f"{s}.{f}"]) == getattr(cls, f).offset, (s, f)
+    out = header_layout(structs, ['printf("tag %u\\n", PGX_SDE_PHILOX_TAG);'])
     assert int(out["tag"]) == abi.SDE_PHILOX_TAG == 0x53444500
     # blocks q < 1024: disjoint from the Actor's and the ActorCritic's counter words
     for other in (abi.ACTOR_PHILOX_TAG, abi.AC_PHILOX_TAG):
@@ -97,15 +80,7 @@ def test_struct_layout_matches_header(tmp_path):
 
 
 def test_library_exports_the_entry_points():
-    lib = _native.load()
-    for name in SDE_EXPORTS:
-        assert hasattr(lib, name), name
-        assert name in _native.EXPORTS, name
-    rt = os.path.join(ROOT, "panda-gym_amd", "libpgx_rtmodel.so")
-    assert os.path.exists(rt), "build() makes the runtime-model library too"
-    rtlib = C.CDLL(rt)
-    for name in SDE_EXPORTS:
-        assert hasattr(rtlib, name), name
+    assert_exported(SDE_EXPORTS)
 
 
 def good_config():
