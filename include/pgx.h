@@ -1058,6 +1058,65 @@ int pgx_actor_forward_host(const pgx_actor_config* cfg, const pgx_actor_weights*
                            const float* achieved_goal, const float* desired_goal, int32_t n, float* mean_out,
                            float* log_std_out);
 
+/* Action log-probability of a batch (GAUSSIAN kind): SB3's actor.action_log_prob(observations), i.e.
+ * SquashedDiagGaussianDistribution.log_prob_from_params, for B rows in one launch.  B is a launch argument,
+ * independent of n_envs; every row-indexed input carries its row stride in floats (row b of `obs` starts at
+ * obs + b * obs_stride), so the fields of a HER batch's rows (pgx_replay_batch.rows) are read where they
+ * lie; nothing batch-sized is kept in the handle.  Kernel launches only (one): it captures as one node.
+ *
+ * Features, trunk, the mu / log_std head tile, the clip_mean clamp and the [-20, 2] clamp: the forward's,
+ * word for word (above).  Epilogue per (row b, dimension d), f32, NO CONTRACTION: every operation is
+ * rounded on its own but the one fmaf written here (device expf / tanhf / logf):
+ *   std = expf(log_std);  g = fmaf(std, eps, mean);  a = tanhf(g)                -> action[b][d]
+ *   z = g - mean
+ *   lp_d = ((-(z * z)) / (2 * (std * std)) - log_std) - 0.9189385f      (torch Normal.log_prob's order)
+ *   c_d  = logf((1 - a * a) + 1e-6f)                                    (SB3: log(1 - actions**2 + epsilon))
+ *   log_prob[b] = (lp_0 + lp_1 + ...) - (c_0 + c_1 + ...)
+ * both sums start at their first term and add in ascending d.
+ *
+ * eps [B, action_dim]: the caller's dense buffer (io.eps), or, with io.eps NULL, the device Philox stream
+ * through the forward's Box-Muller lines (above) with
+ *   r = philox(counter = (word lo, word hi, b, PGX_ACTOR_LP_PHILOX_TAG ^ p), key = (seed lo, seed hi))
+ * where `word` is a 64-bit device word of its own (pgx_actor_lp_state), moved on by one behind the last
+ * read of every launch that draws, inside that launch: every replay of a captured graph draws new noise.
+ * The forward's step word is never touched, and the tag is disjoint from the forward's (0x41435430 ^ p),
+ * the ActorCritic's and the SdeActor's two.
+ * Only action [B, A], log_prob [B] and the non-NULL debug planes are written, rows b < B only. */
+#define PGX_ACTOR_LP_PHILOX_TAG 0x414C5030u
+
+typedef struct pgx_actor_lp_io {
+    const float* obs;             /* [B,obs_dim] */
+    const float* achieved_goal;   /* [B,3] */
+    const float* desired_goal;    /* [B,3] */
+    const float* eps;             /* [B,action_dim] dense, or NULL: the device stream */
+    float* action;                /* [B,action_dim] dense */
+    float* log_prob;              /* [B] */
+    float* mean_out;              /* debug [B,action_dim] or NULL: mean (after clip_mean) */
+    float* log_std_out;           /* debug [B,action_dim] or NULL: log_std after the clamp */
+    float* eps_out;               /* debug [B,action_dim] or NULL: the noise used */
+    float* gaussian_action_out;   /* debug [B,action_dim] or NULL: g */
+    uint32_t* philox_out;         /* debug [B,4,4] or NULL: as pgx_actor_io's, when the stream is drawn from
+                                     (the host model never writes it) */
+    int32_t obs_stride;           /* >= obs_dim */
+    int32_t achieved_goal_stride; /* >= 3 */
+    int32_t desired_goal_stride;  /* >= 3 */
+    int32_t pad0;
+} pgx_actor_lp_io;
+
+/* One launch (see above).  PGX_E_INVALID, before any device call and naming the field, for a
+ * DETERMINISTIC handle (kind), a NULL io / obs / achieved_goal / desired_goal / action / log_prob, B <= 0,
+ * a stride below its width. */
+int pgx_actor_action_log_prob(pgx_actor_handle h, const pgx_actor_lp_io* io, int32_t B, void* stream);
+/* The log-probability noise word after synchronising `stream`; set: synchronises, then writes it. */
+int pgx_actor_lp_state(pgx_actor_handle h, uint64_t* word, void* stream);
+int pgx_actor_lp_set_state(pgx_actor_handle h, uint64_t word, void* stream);
+/* The contract above in plain C++ on host arrays (std::fmaf, host libm; every pointer of io a host pointer,
+ * strides honoured) for n rows, with the device entry's refusals and: a NULL io->eps (the host model has no
+ * stream).  The mean and log_std planes are what the kernel meets bit for bit; the epilogue goes through
+ * another libm.  Never touches a device. */
+int pgx_actor_log_prob_host(const pgx_actor_config* cfg, const pgx_actor_weights* w, const pgx_actor_lp_io* io,
+                            int32_t n);
+
 /* ----------------------------------------------------------------------
  * ActorCritic: stable-baselines3's on-policy ActorCriticPolicy forward on the device
  * (pgx_actor_critic.hip), as MultiInputPolicy instantiates it for these envs (PPO): one launch gives
@@ -1216,7 +1275,7 @@ int pgx_ac_forward_host(const pgx_ac_config* cfg, const pgx_ac_weights* w, const
  * consecutive h of one (env, a), and a wave's loads are contiguous):
  *   S[e / 16][h / 4][e % 16][a][h % 4], H rounded up to 4 and n_envs to 16, padding kept at +0;
  * pgx_sde_actor_get_matrices / _set_matrices translate from and to SB3's [N, H, A] with a kernel.
- * Every entry below but create / destroy / state / set_state enqueues kernel launches only on the
+ * Every entry below but create / destroy / state / set_state (and batch_state / batch_set_state) enqueues kernel launches only on the
  * caller's stream (no memcpy or memset node, no allocation, no sync), so everything captures;
  * pgx_sde_actor_set_weights first copies the parameters into the handle (copy operations on `stream`).
  * ---------------------------------------------------------------------- */
@@ -1281,6 +1340,78 @@ int pgx_sde_actor_get_std(pgx_sde_actor_handle h, float* out, void* stream);
 int pgx_sde_actor_forward_host(const pgx_sde_actor_config* cfg, const pgx_sde_actor_weights* w, const float* obs,
                                const float* achieved_goal, const float* desired_goal, const float* matrices, int32_t n,
                                float* mean_out, float* latent_out, float* noise_out);
+
+/* Action log-probability of a batch: SB3's actor.action_log_prob(observations) on the gSDE distribution
+ * (StateDependentNoiseDistribution.log_prob_from_params) as TQC.train reaches it, for B rows in one
+ * launch.  The batch length differs from the number of per-env matrices, so SB3's get_noise takes the ONE
+ * shared exploration_mat [H, A], not the per-env ones: the handle holds a shared matrix Eb [H, A] beside
+ * them, and std2[h][a] = std[h][a] * std[h][a] (one f32 multiply, computed where std is, at
+ * pgx_sde_actor_set_weights).  B, the row strides, what is written and the capture are as
+ * pgx_actor_action_log_prob's (above).
+ *
+ * latent and mean: the forward's, word for word.  With K16 = H rounded up to 16, per (row b, dimension a):
+ *   noise[b][a] = the Linear chain:  acc = +0;  for h = 0 .. K16 - 1 ascending:  acc = fmaf(latent[b][h],
+ *                 Eb[h][a], acc), the terms h >= H being fmaf(+0, +0, acc)
+ *   var[b][a]   = the same chain over sq[b][h] = latent[b][h] * latent[b][h] (one f32 multiply) against std2[h][a]
+ *   (Both are the mu Linear's chain with bias +0, so the kernel's MFMA carries them: Eb is packed into rows
+ *   8..14 of mu's tile, std2 into a tile of its own.  The per-env forward's noise chain has exactly H terms:
+ *   with the same matrix the two agree bit for bit where H is a multiple of 16, and elsewhere but for a -0
+ *   sum, which the +0 padding turns into +0.)
+ * then in f32, no contraction, every operation rounded on its own (device sqrtf / tanhf / log1pf / logf):
+ *   scale = sqrtf(var + 1e-6f)                                  (SB3: sqrt(variance + epsilon))
+ *   a = tanhf(mean + noise)                                                       -> action[b][a]
+ *   x = a < -(1 - EPS) ? -(1 - EPS) : a > (1 - EPS) ? (1 - EPS) : a,   EPS = 1.1920929e-7f
+ *   g' = 0.5f * (log1pf(x) - log1pf(-x))        (TanhBijector.inverse: SB3's gSDE path recovers the Gaussian
+ *                                                action from the squashed one)
+ *   z = g' - mean
+ *   lp_a = ((-(z * z)) / (2 * (scale * scale)) - logf(scale)) - 0.9189385f
+ *   t = tanhf(g');  c_a = logf((1 - t * t) + 1e-6f)
+ *   log_prob[b] = (lp_0 + lp_1 + ...) - (c_0 + c_1 + ...)   both sums from their first term, ascending a
+ *
+ * pgx_sde_actor_reset_batch_noise draws Eb = eps * std in one launch (SB3 actor.reset_noise() at the top of a
+ * gradient step: sample_weights' exploration_mat): for flat index j = h * A + a and block q = j / 4,
+ *   r = philox4x32_10(counter = (bgen lo, bgen hi, 0, PGX_SDE_BATCH_PHILOX_TAG ^ q), key = (seed lo, seed hi))
+ * and the per-env draw's lines from there.  `bgen` is a 64-bit device word of its own
+ * (pgx_sde_actor_batch_state) that the launch moves on by one.  PGX_SDE_BATCH_PHILOX_TAG ^ q, q < 1024, spans
+ * 0x53444000 .. 0x534443FF; PGX_SDE_PHILOX_TAG ^ q spans 0x53444400 .. 0x534447FF.  The per-env matrices,
+ * their generation word and pgx_sde_actor_reset_noise are untouched by all of this. */
+#define PGX_SDE_BATCH_PHILOX_TAG 0x53444200u
+
+typedef struct pgx_sde_actor_lp_io {
+    const float* obs;             /* [B,obs_dim] */
+    const float* achieved_goal;   /* [B,3] */
+    const float* desired_goal;    /* [B,3] */
+    float* action;                /* [B,action_dim] dense */
+    float* log_prob;              /* [B] */
+    float* mean_out;              /* debug [B,action_dim] or NULL: mean (after clip_mean) */
+    float* latent_out;            /* debug [B,H] or NULL */
+    float* noise_out;             /* debug [B,action_dim] or NULL */
+    float* variance_out;          /* debug [B,action_dim] or NULL: var */
+    float* gaussian_action_out;   /* debug [B,action_dim] or NULL: g' */
+    int32_t obs_stride;           /* >= obs_dim */
+    int32_t achieved_goal_stride; /* >= 3 */
+    int32_t desired_goal_stride;  /* >= 3 */
+    int32_t pad0;
+} pgx_sde_actor_lp_io;
+
+/* One launch (see above).  PGX_E_INVALID, before any device call and naming the field, for a NULL io / obs /
+ * achieved_goal / desired_goal / action / log_prob, B <= 0, a stride below its width. */
+int pgx_sde_actor_action_log_prob(pgx_sde_actor_handle h, const pgx_sde_actor_lp_io* io, int32_t B, void* stream);
+/* One launch: Eb from `bgen`, which it moves on by one.  Debug (device, or NULL): eps_out [H, A] f32. */
+int pgx_sde_actor_reset_batch_noise(pgx_sde_actor_handle h, float* eps_out, void* stream);
+/* Eb as SB3 lays exploration_mat out, device f32 [H, A]: one launch each on `stream`. */
+int pgx_sde_actor_get_batch_matrix(pgx_sde_actor_handle h, float* out, void* stream);
+int pgx_sde_actor_set_batch_matrix(pgx_sde_actor_handle h, const float* in, void* stream);
+/* The batch generation word after synchronising `stream`; set: synchronises, then writes it. */
+int pgx_sde_actor_batch_state(pgx_sde_actor_handle h, uint64_t* generation, void* stream);
+int pgx_sde_actor_batch_set_state(pgx_sde_actor_handle h, uint64_t generation, void* stream);
+/* The contract above in plain C++ on host arrays (std::fmaf, host libm; every pointer a host pointer, strides
+ * honoured) for n rows, with the device entry's refusals and: a NULL exploration_mat.  std [H, A]: what the
+ * handle holds (pgx_sde_actor_get_std), or NULL: expf(w->log_std) by the host's libm.  The mean, latent,
+ * noise and variance planes are what the kernel meets bit for bit; the epilogue goes through another libm.
+ * Never touches a device. */
+int pgx_sde_actor_log_prob_host(const pgx_sde_actor_config* cfg, const pgx_sde_actor_weights* w, const float* std,
+                                const float* exploration_mat, const pgx_sde_actor_lp_io* io, int32_t n);
 
 /* ----------------------------------------------------------------------
  * QuantileCritic: sb3_contrib TQC's quantile critics on the device (pgx_quantile_critic.hip): the

@@ -102,6 +102,10 @@ SIGNATURES: Dict[str, Tuple[list, Any]] = {
     "pgx_actor_state": _int(P, ptr(U64), P),
     "pgx_actor_set_state": _int(P, U64, P),
     "pgx_actor_forward_host": _int(ptr(abi.PgxActorConfig), ptr(abi.PgxActorWeights), P, P, P, I32, P, P),
+    "pgx_actor_action_log_prob": _int(P, ptr(abi.PgxActorLpIo), I32, P),
+    "pgx_actor_lp_state": _int(P, ptr(U64), P),
+    "pgx_actor_lp_set_state": _int(P, U64, P),
+    "pgx_actor_log_prob_host": _int(ptr(abi.PgxActorConfig), ptr(abi.PgxActorWeights), ptr(abi.PgxActorLpIo), I32),
 
     "pgx_ac_create": _int(ptr(abi.PgxAcConfig), C.c_int, ptr(P)),
     "pgx_ac_destroy": ([P], None),
@@ -124,6 +128,14 @@ SIGNATURES: Dict[str, Tuple[list, Any]] = {
     "pgx_sde_actor_get_std": _int(P, P, P),
     "pgx_sde_actor_forward_host": _int(ptr(abi.PgxSdeActorConfig), ptr(abi.PgxSdeActorWeights), P, P, P, P, I32,
                                        P, P, P),
+    "pgx_sde_actor_action_log_prob": _int(P, ptr(abi.PgxSdeActorLpIo), I32, P),
+    "pgx_sde_actor_reset_batch_noise": _int(P, P, P),
+    "pgx_sde_actor_get_batch_matrix": _int(P, P, P),
+    "pgx_sde_actor_set_batch_matrix": _int(P, P, P),
+    "pgx_sde_actor_batch_state": _int(P, ptr(U64), P),
+    "pgx_sde_actor_batch_set_state": _int(P, U64, P),
+    "pgx_sde_actor_log_prob_host": _int(ptr(abi.PgxSdeActorConfig), ptr(abi.PgxSdeActorWeights), P, P,
+                                        ptr(abi.PgxSdeActorLpIo), I32),
 
     "pgx_qc_create": _int(ptr(abi.PgxQcConfig), C.c_int, ptr(P)),
     "pgx_qc_destroy": ([P], None),

@@ -13,6 +13,7 @@ import numpy as np
 
 from ._handle import OBS_KEYS, Handle, torch  # noqa: F401  (OBS_KEYS, torch: importable from here as before)
 from ._native import PgxError, load
+from .abi import ptr as abi_ptr
 
 
 class Policy(Handle):
@@ -111,6 +112,97 @@ class Policy(Handle):
 
     def _obs(self, obs: Dict[str, Any]) -> Dict[str, "torch.Tensor"]:
         return {k: self._dev(obs[k], self._obs_shape(k)) for k in OBS_KEYS}
+
+    def _field(self, x, width: int, B: Optional[int], name: str):
+        """A row-indexed input as (tensor, row stride in floats): a device f32 tensor [B, width] (or [B] for
+        width 1) whose rows are contiguous is read in place, whatever its row stride; anything else is
+        copied to a dense one."""
+        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+        if t.dim() == 1 and width == 1:
+            t = t.unsqueeze(1)
+        if t.dim() != 2 or t.shape[1] != width or (B is not None and t.shape[0] != B):
+            raise ValueError(f"{name}: expected shape [{'B' if B is None else B}, {width}], got {list(t.shape)}")
+        ok = t.dtype == torch.float32 and t.device == self.device and (width == 1 or t.stride(1) == 1) \
+            and (t.shape[0] == 1 or t.stride(0) >= width)
+        if not ok:
+            t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        return t, (width if t.shape[0] == 1 else int(t.stride(0)))
+
+    # ------------------------------------------------- action log-probability (Actor, SdeActor)
+    _LP_PHILOX = False   # the unit draws its noise inside the launch and can record the words
+
+    def _lp_planes(self) -> Dict[str, int]:
+        """Name -> width of the debug planes of ``action_log_prob``."""
+        raise PgxError(f"{type(self).__name__} has no action_log_prob")
+
+    def _lp_io(self, io, obs: Dict[str, Any], out):
+        """Fills a batch launch's ``io`` (``PgxActorLpIo`` / ``PgxSdeActorLpIo``): the observation fields with
+        their row strides, read in place where they can be, and the outputs ``(actions [B, A], log_prob
+        [B])``, ``out`` or new tensors.  Returns (B, actions, log_prob, what the launch reads)."""
+        o, io.obs_stride = self._field(obs["observation"], self.obs_dim, None, "observation")
+        B = int(o.shape[0])
+        ag, io.achieved_goal_stride = self._field(obs["achieved_goal"], 3, B, "achieved_goal")
+        dg, io.desired_goal_stride = self._field(obs["desired_goal"], 3, B, "desired_goal")
+        if out is None:
+            act = torch.empty((B, self.action_dim), dtype=torch.float32, device=self.device)
+            lp = torch.empty((B,), dtype=torch.float32, device=self.device)
+        else:
+            act, lp = out
+            for t, tail in ((act, (self.action_dim,)), (lp, ())):
+                if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != self.device \
+                        or not t.is_contiguous() or t.dim() != 1 + len(tail) or t.shape[0] < B \
+                        or tuple(t.shape[1:]) != tail:
+                    raise ValueError(f"out must be contiguous f32 tensors [>= {B}, {self.action_dim}] and [>= {B}] "
+                                     f"on {self.device} (rows past {B} are left alone)")
+        io.obs, io.achieved_goal, io.desired_goal = o.data_ptr(), ag.data_ptr(), dg.data_ptr()
+        io.action, io.log_prob = act.data_ptr(), lp.data_ptr()
+        return B, act, lp, [o, ag, dg]
+
+    def enable_log_prob_debug(self, B: int) -> Dict[str, "torch.Tensor"]:
+        """Allocate the debug planes every later ``action_log_prob`` of ``B`` rows fills: f32 [B, width] per
+        name of ``_lp_planes()``, and ``philox`` [B, 4, 4] int32 where the unit draws its noise in that
+        launch.  Tests and tools only; ``None`` turns them off."""
+        self._need_device()
+        if B is None:
+            self._lp_debug = None
+            return {}
+        z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=self.device)  # noqa: E731
+        d = {k: z(int(B), w) for k, w in self._lp_planes().items()}
+        if self._LP_PHILOX:
+            d["philox"] = z(int(B), 4, 4, dt=torch.int32)
+        self._lp_debug = d
+        return d
+
+    def _lp_debug_into(self, io, B: int) -> None:
+        d = getattr(self, "_lp_debug", None)
+        if d is None:
+            return
+        if next(iter(d.values())).shape[0] != B:
+            raise ValueError(f"the debug planes hold {next(iter(d.values())).shape[0]} rows, the batch {B}")
+        for k, t in d.items():
+            setattr(io, f"{k}_out", t.data_ptr())
+
+    @staticmethod
+    def _batch_obs(batch: Dict[str, "torch.Tensor"], next: bool) -> Dict[str, "torch.Tensor"]:
+        """The observation dict of a HER batch (``buf.alloc_batch``): its ``next_*`` fields, or the current ones."""
+        p = "next_" if next else ""
+        return {"observation": batch[p + "obs"], "achieved_goal": batch[p + "achieved_goal"],
+                "desired_goal": batch[p + "desired_goal"]}
+
+    def _host_lp_io(self, io, obs: Dict[str, Any], planes: Dict[str, int]):
+        """Fills ``io`` for a host model: dense numpy inputs, and every output and plane as a new array.
+        Returns (n, {name: array})."""
+        o, n = self._host_obs(obs)
+        io.obs, io.achieved_goal, io.desired_goal = (abi_ptr(o["observation"]), abi_ptr(o["achieved_goal"]),
+                                                     abi_ptr(o["desired_goal"]))
+        io.obs_stride, io.achieved_goal_stride, io.desired_goal_stride = self.obs_dim, 3, 3
+        res = {"action": np.zeros((n, self.action_dim), np.float32), "log_prob": np.zeros((n,), np.float32)}
+        io.action, io.log_prob = abi_ptr(res["action"]), abi_ptr(res["log_prob"])
+        for k, w in planes.items():
+            res[k] = np.zeros((n, w), np.float32)
+            setattr(io, f"{k}_out", abi_ptr(res[k]))
+        res["_keep"] = o
+        return n, res
 
     @staticmethod
     def _host_obs(obs: Dict[str, Any]):

@@ -283,8 +283,32 @@ class PgxActorIo(C.Structure):
     ]
 
 
+ACTOR_LP_PHILOX_TAG = 0x414C5030   # PGX_ACTOR_LP_PHILOX_TAG: the action_log_prob stream's counter word 3
+
+
+class PgxActorLpIo(C.Structure):
+    _fields_ = [
+        ("obs", C.c_void_p), ("achieved_goal", C.c_void_p), ("desired_goal", C.c_void_p), ("eps", C.c_void_p),
+        ("action", C.c_void_p), ("log_prob", C.c_void_p), ("mean_out", C.c_void_p), ("log_std_out", C.c_void_p),
+        ("eps_out", C.c_void_p), ("gaussian_action_out", C.c_void_p), ("philox_out", C.c_void_p),
+        ("obs_stride", C.c_int32), ("achieved_goal_stride", C.c_int32), ("desired_goal_stride", C.c_int32),
+        ("pad0", C.c_int32),
+    ]
+
+
 # SdeActor (include/pgx.h, pgx_sde_actor_*)
 SDE_PHILOX_TAG = 0x53444500   # PGX_SDE_PHILOX_TAG: counter word 3 of the matrix draw, xor the block q
+SDE_BATCH_PHILOX_TAG = 0x53444200   # PGX_SDE_BATCH_PHILOX_TAG: the same of the shared batch matrix's draw
+
+
+class PgxSdeActorLpIo(C.Structure):
+    _fields_ = [
+        ("obs", C.c_void_p), ("achieved_goal", C.c_void_p), ("desired_goal", C.c_void_p), ("action", C.c_void_p),
+        ("log_prob", C.c_void_p), ("mean_out", C.c_void_p), ("latent_out", C.c_void_p), ("noise_out", C.c_void_p),
+        ("variance_out", C.c_void_p), ("gaussian_action_out", C.c_void_p),
+        ("obs_stride", C.c_int32), ("achieved_goal_stride", C.c_int32), ("desired_goal_stride", C.c_int32),
+        ("pad0", C.c_int32),
+    ]
 
 
 class PgxSdeActorConfig(C.Structure):

@@ -11,6 +11,10 @@ of an env or a wrapper and writes the action buffer the next step reads, so ``ca
 ``device="cpu"`` an ``Actor`` only holds and maps parameters (``load_state_dict`` / ``state_dict`` /
 ``forward_host``, the host model of the kernel's arithmetic, which is a test oracle and not a way to step).
 
+``action_log_prob`` is SB3's ``actor.action_log_prob(observations)`` for the Gaussian kind: actions and their
+log-probability for a batch of any size in one launch, a HER batch's rows read in place
+(``action_log_prob_rows``) -- the ``next_actions`` / ``next_log_prob`` of ``TQC.train``'s target.
+
 PPO's actor-critic lives next door (actor_critic.py), the gSDE actor (``use_sde=True``, per-env exploration
 matrices) in sde_actor.py, TQC's critics (forward, truncated TD target, Polyak step) in quantile_critic.py.
 Optimisers are not here.
@@ -147,6 +151,67 @@ class Actor(Policy):
 
     noise_step = property(Policy._get_word, Policy._set_word, doc="""The device word that counts the forwards that
         drew noise from the Philox stream (this synchronises).  Setting it back reproduces the draws.""")
+
+    # ------------------------------------------------- action log-probability
+    _LP_PHILOX = True
+
+    def _lp_planes(self) -> Dict[str, int]:
+        return {k: self.action_dim for k in ("mean", "log_std", "eps", "gaussian_action")}
+
+    def action_log_prob(self, obs: Dict[str, Any], eps: Any = None, out=None):
+        """SB3's ``actor.action_log_prob(obs)`` for the Gaussian kind: ``(actions [B, A], log_prob [B])`` of a
+        batch of any size ``B``, one launch.  ``obs``: an observation dict of [B, .] tensors; device f32
+        tensors with contiguous rows, views into a HER batch's rows included, are read in place.  ``eps``
+        [B, A]: the Gaussian noise to use instead of the device stream (``log_prob_noise_step``, which a
+        launch that draws moves on by one: a replayed graph draws new noise).  ``out``: a pair of
+        contiguous f32 tensors [B, A] and [B] to fill (returned as they are)."""
+        self._need_device()
+        io = abi.PgxActorLpIo()
+        B, act, lp, keep = self._lp_io(io, obs, out)
+        e = None if eps is None else self._dev(eps, (B, self.action_dim))
+        if e is not None:
+            io.eps = e.data_ptr()
+        self._lp_debug_into(io, B)
+        check(self.lib.pgx_actor_action_log_prob(self._h, C.byref(io), B, self._stream()), "pgx_actor_action_log_prob",
+              self.lib)
+        self._keep = keep + [e, act, lp]   # alive until the stream has consumed them
+        return act, lp
+
+    def action_log_prob_rows(self, batch: Dict[str, "torch.Tensor"], next: bool = True, out=None):
+        """``action_log_prob`` on a HER batch (``buf.alloc_batch`` / ``buf.sample_into``): ``next_obs``,
+        ``next_achieved_goal`` and ``next_desired_goal`` (``next=False``: ``obs``, ``achieved_goal``,
+        ``desired_goal``) are read from ``batch["rows"]`` in place."""
+        return self.action_log_prob(self._batch_obs(batch, next), out=out)
+
+    def _get_lp_word(self) -> int:
+        self._need_device()
+        v = C.c_uint64(0)
+        self._call("lp_state", self._h, C.byref(v), self._stream())
+        return int(v.value)
+
+    def _set_lp_word(self, value: int) -> None:
+        self._need_device()
+        self._call("lp_set_state", self._h, C.c_uint64(int(value) & 0xFFFFFFFFFFFFFFFF), self._stream())
+
+    log_prob_noise_step = property(_get_lp_word, _set_lp_word, doc="""The device word that counts the
+        ``action_log_prob`` launches that drew noise from the Philox stream (this synchronises); ``noise_step``
+        is another word.  Setting it back reproduces the draws.""")
+
+    def log_prob_host(self, obs: Dict[str, Any], eps: Any) -> Dict[str, np.ndarray]:
+        """The library's host model of ``action_log_prob`` for any number of rows and their ``eps`` [n, A]:
+        ``action``, ``log_prob`` and the planes ``mean``, ``log_std``, ``eps``, ``gaussian_action`` as numpy
+        f32.  ``mean`` and ``log_std`` are what the kernel gives bit for bit.  A test oracle."""
+        ws, bs = self._host_params()
+        w = self._weights_struct([x.ctypes.data for x in ws], [x.ctypes.data for x in bs])
+        io = abi.PgxActorLpIo()
+        n, res = self._host_lp_io(io, obs, self._lp_planes())
+        e = np.ascontiguousarray(eps.cpu().numpy() if torch.is_tensor(eps) else eps, dtype=np.float32)
+        if e.shape != (n, self.action_dim):
+            raise ValueError(f"expected eps of shape {[n, self.action_dim]}, got {list(e.shape)}")
+        io.eps = abi.ptr(e)
+        self._call("log_prob_host", C.byref(self._cfg), C.byref(w), C.byref(io), n)
+        del res["_keep"]
+        return res
 
     # --------------------------------------------------------------- capture
     def capture_rollout(self, venv, k: int, deterministic: bool = False, after_step: Optional[Callable[[], None]] = None):

@@ -20,10 +20,20 @@
  * The staging, the Linear, the loop over the layers, the Gaussian draw and the noise step word's read
  * and advance are pgx_mlp.h's, shared with the other policy units; the epilogue is this unit's.  The
  * host-side plan, allocation and packing are pgx_policy.h's.
+ *
+ * Log-probability kernel (pgx_actor_action_log_prob, SB3's actor.action_log_prob): the same workgroup
+ * over a tile of 32 batch rows (16 for a batch of up to 16, or where 32 do not fit the LDS), the batch
+ * size a launch argument and every observation field read through its own row stride (pgx_mlp.h's
+ * stage_features_rows).  Behind the head tile the thread of (row, dimension) computes the squashed action
+ * and its two log-probability terms with contraction off; the terms go through the dead activations
+ * and the thread of dimension 0 adds them in ascending order.  Its noise word is another than the
+ * forward's.
  */
 #include "pgx_policy.h"   /* pgx_mlp.h, pgx_common.h, include/pgx.h */
 
-int pgx_actor_check_config(const pgx_actor_config* c, const char* what, bool with_envs);  /* pgx_actor_host.cpp */
+/* pgx_actor_host.cpp */
+int pgx_actor_check_config(const pgx_actor_config* c, const char* what, bool with_envs);
+int pgx_actor_lp_check_launch(const pgx_actor_config* c, const pgx_actor_lp_io* io, int32_t B, const char* what);
 
 namespace {
 
@@ -84,6 +94,60 @@ __global__ __launch_bounds__(THREADS) void actor_forward_kernel(ActorArgs a, pgx
     advance_word(a.step, a.ticket, &sh_step, gridDim.x, draw, tid);
 }
 
+/* the log-probability epilogue of one (row, dimension), every operation rounded on its own but the fmaf */
+__device__ __forceinline__ void lp_terms(float mean, float ls, float eps, float* g, float* act, float* lp, float* c) {
+#pragma clang fp contract(off)
+    const float std = expf(ls);
+    *g = __builtin_fmaf(std, eps, mean);
+    const float t = tanhf(*g);
+    const float z = *g - mean;
+    *lp = ((-(z * z)) / (2.0f * (std * std)) - ls) - 0.9189385f;
+    *c = logf((1.0f - t * t) + 1e-6f);
+    *act = t;
+}
+
+/* pgx_actor_action_log_prob: the forward's workgroup over a tile of batch rows read through their strides;
+ * a.n is the batch size, a.step / a.ticket the log-probability noise word and its ticket */
+template <int MT>
+__global__ __launch_bounds__(THREADS) void actor_lp_kernel(ActorArgs a, pgx_actor_lp_io io) {
+    extern __shared__ float lds[];
+    __shared__ unsigned long long sh_step;
+    constexpr int ROWS = MT * 16;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int S = a.S, B = a.n, A = a.ad;
+    const int row0 = blockIdx.x * ROWS;
+    const bool draw = io.eps == nullptr;
+    load_word(&sh_step, a.step, draw, tid);
+    stage_features_rows<MT>(lds, io.obs, io.achieved_goal, io.desired_goal, io.obs_stride, io.achieved_goal_stride,
+                            io.desired_goal_stride, row0, B, a.od, a.plan.nkb[0] * 16, S, tid);
+    __syncthreads();
+    const int in_off = run_linears<MT>(lds, a.params, a.plan, a.plan.n_linear, false, 0, S, ROWS * S, 0, S, lane, wave);
+    /* one thread per (row, dimension); the head tile lies at lds[in_off] */
+    const int r = tid >> 3, d = tid & 7;
+    const int b = row0 + r;
+    const bool own = r < ROWS && d < A && b < B;
+    float lp = 0.0f, c = 0.0f;
+    if (own) {
+        const float* head = lds + in_off + r * S;
+        float mean = head[d];
+        if (a.clip > 0.0f) mean = mean < -a.clip ? -a.clip : (mean > a.clip ? a.clip : mean);
+        const float v = head[LOG_STD_ROW + d];
+        const float ls = v < PGX_ACTOR_LOG_STD_MIN ? PGX_ACTOR_LOG_STD_MIN : (v > PGX_ACTOR_LOG_STD_MAX ? PGX_ACTOR_LOG_STD_MAX : v);
+        const size_t o = (size_t)b * A + d;
+        const float eps = io.eps ? io.eps[o] : gaussian_draw(sh_step, b, d, PGX_ACTOR_LP_PHILOX_TAG, a.seed_lo, a.seed_hi, io.philox_out);
+        float g, act;
+        lp_terms(mean, ls, eps, &g, &act, &lp, &c);
+        io.action[o] = act;
+        if (io.mean_out) io.mean_out[o] = mean;
+        if (io.log_std_out) io.log_std_out[o] = ls;
+        if (io.eps_out) io.eps_out[o] = eps;
+        if (io.gaussian_action_out) io.gaussian_action_out[o] = g;
+    }
+    __syncthreads();   /* the head tile is read: the activations are dead and carry the sums' terms */
+    sum_log_prob(lds, lp, c, own, A, io.log_prob, (size_t)b, tid);
+    advance_word(a.step, a.ticket, &sh_step, gridDim.x, draw, tid);
+}
+
 }  // namespace
 
 struct pgx_actor {
@@ -95,6 +159,14 @@ struct pgx_actor {
     size_t plain_w[5], plain_b[5];   /* per slot: the hidden layers, mu, log_std */
     int mt;                     /* env tiles of 16 per workgroup */
     size_t lds_bytes;
+    unsigned long long* lp_step;   /* the log-probability noise word and its ticket, in the words' region */
+    uint32_t* lp_ticket;
+
+    size_t lds_need(int mt) const { return 2 * (size_t)mt * 16 * a.S * 4; }
+    /* row tiles of 16 per workgroup of a batch launch: 32 rows from 17 on, where they fit the LDS */
+    int lp_tile(int B) const {
+        return choose_tile(B, "PGX_ACTOR_LP_TILE", [this](int mt) { return lds_need(mt); }, 17);
+    }
 };
 
 extern "C" {
@@ -146,6 +218,21 @@ int pgx_actor_create(const pgx_actor_config* cfg, int device, pgx_actor_handle* 
     h->plain = (float*)ptr[1];
     a.step = (unsigned long long*)ptr[2];
     a.ticket = (uint32_t*)((char*)ptr[2] + 8);
+    h->lp_step = (unsigned long long*)((char*)ptr[2] + 16);
+    h->lp_ticket = (uint32_t*)((char*)ptr[2] + 24);
+    if (cfg->kind == PGX_ACTOR_GAUSSIAN) {   /* the batch kernels' dynamic LDS: 16 rows always fit, 32 where they do */
+        const int mt_max = choose_tile(17, nullptr, [h](int mt) { return h->lds_need(mt); }, 17);
+        bool ok = hipFuncSetAttribute((const void*)actor_lp_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)h->lds_need(1)) == hipSuccess;
+        if (mt_max == 2)
+            ok = ok && hipFuncSetAttribute((const void*)actor_lp_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)h->lds_need(2)) == hipSuccess;
+        if (!ok) {
+            (void)hipFree(h->params);
+            delete h;
+            return pgx_set_error(PGX_E_HIP, "pgx_actor_create: device setup failed");
+        }
+    }
     *out = h;
     return PGX_OK;
 }
@@ -183,6 +270,30 @@ int pgx_actor_forward(pgx_actor_handle h, const pgx_actor_io* io, int32_t determ
     launch_tiles(actor_forward_kernel<1>, actor_forward_kernel<2>, h->mt, h->a.n, h->lds_bytes, stream, h->a, *io,
                  deterministic);
     return hipGetLastError() == hipSuccess ? PGX_OK : pgx_set_error(PGX_E_HIP, "pgx_actor_forward: launch failed");
+}
+
+int pgx_actor_action_log_prob(pgx_actor_handle h, const pgx_actor_lp_io* io, int32_t B, void* stream) {
+    const char* what = "pgx_actor_action_log_prob";
+    if (!h) return fail(PGX_E_INVALID, what, "null handle");
+    const int rc = pgx_actor_lp_check_launch(&h->cfg, io, B, what);
+    if (rc != PGX_OK) return rc;
+    ActorArgs a = h->a;
+    a.n = B;
+    a.step = h->lp_step;
+    a.ticket = h->lp_ticket;
+    const int mt = h->lp_tile(B);
+    launch_tiles(actor_lp_kernel<1>, actor_lp_kernel<2>, mt, B, h->lds_need(mt), stream, a, *io);
+    return hipGetLastError() == hipSuccess ? PGX_OK : fail(PGX_E_HIP, what, "launch failed");
+}
+
+int pgx_actor_lp_state(pgx_actor_handle h, uint64_t* word, void* stream) {
+    if (!h || !word) return pgx_set_error(PGX_E_INVALID, "pgx_actor_lp_state: null handle or word pointer");
+    return read_word("pgx_actor_lp_state", h->lp_step, word, stream);
+}
+
+int pgx_actor_lp_set_state(pgx_actor_handle h, uint64_t word, void* stream) {
+    if (!h) return pgx_set_error(PGX_E_INVALID, "pgx_actor_lp_set_state: null handle");
+    return write_word("pgx_actor_lp_set_state", h->lp_step, word, stream);
 }
 
 int pgx_actor_state(pgx_actor_handle h, uint64_t* step, void* stream) {

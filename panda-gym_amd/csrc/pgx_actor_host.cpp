@@ -12,7 +12,11 @@
  * `check_common`, `check_count` and `check_widths`.  pgx_qc_forward_host and pgx_qc_target_host (last) are
  * the quantile critics' (pgx_quantile_critic.hip): the same Linears, then the pooled sort by the order
  * rule's key, the truncation and the unfused Bellman backup; the launch checks they share with the device
- * entry points are pgx_qc_check_launch.
+ * entry points are pgx_qc_check_launch.  pgx_actor_log_prob_host and pgx_sde_actor_log_prob_host are the
+ * action log-probability entries' contracts (the Actor's and the SdeActor's batch launches): the forward's
+ * planes, the padded noise and variance chains of the gSDE distribution, and the unfused epilogues through
+ * the host's libm; their launch checks, pgx_actor_lp_check_launch and pgx_sde_actor_lp_check_launch, are the
+ * device entries' too.
  */
 #include <algorithm>
 #include <cmath>
@@ -149,6 +153,116 @@ extern "C" int pgx_actor_forward_host(const pgx_actor_config* cfg, const pgx_act
     return PGX_OK;
 }
 
+namespace {
+
+/* what the two action_log_prob launches share: io's pointers and strides, B */
+template <class Io>
+int check_lp_io(const Io* io, int32_t B, int obs_dim, const char* what) {
+    if (!io) return bad(what, "null io");
+    if (!io->obs) return bad(what, "null obs");
+    if (!io->achieved_goal) return bad(what, "null achieved_goal");
+    if (!io->desired_goal) return bad(what, "null desired_goal");
+    if (!io->action) return bad(what, "null action");
+    if (!io->log_prob) return bad(what, "null log_prob");
+    if (B <= 0) return bad(what, "B must be > 0");
+    if (io->obs_stride < obs_dim) return bad(what, "obs_stride is below obs_dim");
+    if (io->achieved_goal_stride < 3) return bad(what, "achieved_goal_stride is below 3");
+    if (io->desired_goal_stride < 3) return bad(what, "desired_goal_stride is below 3");
+    return PGX_OK;
+}
+
+/* x [od + 6] of row b through the strides */
+template <class Io>
+void stage_x_rows(float* x, const Io* io, size_t b, int od) {
+    for (int k = 0; k < 3; k++) x[k] = io->achieved_goal[b * io->achieved_goal_stride + k];
+    for (int k = 0; k < 3; k++) x[3 + k] = io->desired_goal[b * io->desired_goal_stride + k];
+    for (int k = 0; k < od; k++) x[6 + k] = io->obs[b * io->obs_stride + k];
+}
+
+float clip_to(float m, float clip) { return clip > 0.0f ? (m < -clip ? -clip : (m > clip ? clip : m)) : m; }
+
+/* the epilogues of include/pgx.h, every operation rounded on its own but the one fmaf */
+#pragma clang fp contract(off)
+void lp_terms(float mean, float ls, float eps, float* g, float* act, float* lp, float* c) {
+    const float std = std::exp(ls);
+    *g = std::fmaf(std, eps, mean);
+    const float t = std::tanh(*g);
+    const float z = *g - mean;
+    *lp = ((-(z * z)) / (2.0f * (std * std)) - ls) - 0.9189385f;
+    *c = std::log((1.0f - t * t) + 1e-6f);
+    *act = t;
+}
+
+void sde_lp_terms(float mean, float noise, float var, float* act, float* gp, float* lp, float* c) {
+    const float scale = std::sqrt(var + 1e-6f);
+    const float a = std::tanh(mean + noise);
+    const float lim = 1.0f - 1.1920929e-7f;
+    const float x = a < -lim ? -lim : (a > lim ? lim : a);
+    const float g = 0.5f * (std::log1p(x) - std::log1p(-x));
+    const float z = g - mean;
+    *lp = ((-(z * z)) / (2.0f * (scale * scale)) - std::log(scale)) - 0.9189385f;
+    const float t = std::tanh(g);
+    *c = std::log((1.0f - t * t) + 1e-6f);
+    *act = a;
+    *gp = g;
+}
+
+/* (lp_0 + lp_1 + ...) - (c_0 + c_1 + ...), each sum from its first term in ascending d */
+float sum_log_prob(const float* lp, const float* c, int A) {
+    float s_lp = lp[0], s_c = c[0];
+    for (int d = 1; d < A; d++) {
+        s_lp = s_lp + lp[d];
+        s_c = s_c + c[d];
+    }
+    return s_lp - s_c;
+}
+#pragma clang fp contract(on)
+
+}  // namespace
+
+/* the checks of one pgx_actor_action_log_prob launch, device and host alike */
+int pgx_actor_lp_check_launch(const pgx_actor_config* c, const pgx_actor_lp_io* io, int32_t B, const char* what) {
+    if (c->kind != PGX_ACTOR_GAUSSIAN) return bad(what, "kind must be PGX_ACTOR_GAUSSIAN: a DETERMINISTIC actor has no log-probability");
+    return check_lp_io(io, B, c->obs_dim, what);
+}
+
+extern "C" int pgx_actor_log_prob_host(const pgx_actor_config* cfg, const pgx_actor_weights* w, const pgx_actor_lp_io* io,
+                                       int32_t n) {
+    const char* what = "pgx_actor_log_prob_host";
+    int rc = pgx_actor_check_config(cfg, what, false);
+    if (rc == PGX_OK) rc = pgx_actor_lp_check_launch(cfg, io, n, what);
+    if (rc != PGX_OK) return rc;
+    if (!io->eps) return bad(what, "null eps");
+    if (!w) return bad(what, "null weights");
+    const int nl = cfg->n_layers, A = cfg->action_dim, od = cfg->obs_dim, K = cfg->hidden[nl - 1];
+    for (int l = 0; l < nl + 2; l++)
+        if (!w->weight[l] || !w->bias[l]) return bad(what, "null weight or bias pointer");
+    const float clip = (float)cfg->clip_mean;
+    std::vector<float> x(od + 6), y(PGX_ACTOR_MAX_WIDTH), z(PGX_ACTOR_MAX_WIDTH);
+    for (int32_t b = 0; b < n; b++) {
+        stage_x_rows(x.data(), io, (size_t)b, od);
+        const float* in = hidden_layers(nl, cfg->hidden, w->weight, w->bias, x.data(), od + 6, y.data(), z.data());
+        float mu[PGX_ACTOR_MAX_ACTION], ls[PGX_ACTOR_MAX_ACTION], lp[PGX_ACTOR_MAX_ACTION], c[PGX_ACTOR_MAX_ACTION];
+        linear(w->weight[nl], w->bias[nl], in, K, A, false, mu);
+        linear(w->weight[nl + 1], w->bias[nl + 1], in, K, A, false, ls);
+        for (int d = 0; d < A; d++) {
+            const size_t o = (size_t)b * A + d;
+            const float mean = clip_to(mu[d], clip);
+            const float v = ls[d];
+            const float log_std = v < PGX_ACTOR_LOG_STD_MIN ? PGX_ACTOR_LOG_STD_MIN : (v > PGX_ACTOR_LOG_STD_MAX ? PGX_ACTOR_LOG_STD_MAX : v);
+            float g, act;
+            lp_terms(mean, log_std, io->eps[o], &g, &act, &lp[d], &c[d]);
+            io->action[o] = act;
+            if (io->mean_out) io->mean_out[o] = mean;
+            if (io->log_std_out) io->log_std_out[o] = log_std;
+            if (io->eps_out) io->eps_out[o] = io->eps[o];
+            if (io->gaussian_action_out) io->gaussian_action_out[o] = g;
+        }
+        io->log_prob[b] = sum_log_prob(lp, c, A);
+    }
+    return PGX_OK;
+}
+
 /* ---------------------------------------------------------------- ActorCritic (include/pgx.h) */
 
 /* pgx_ac_create's checks (no device call); `what` names the entry point */
@@ -252,6 +366,66 @@ extern "C" int pgx_sde_actor_forward_host(const pgx_sde_actor_config* cfg, const
                 noise_out[(size_t)e * A + d] = acc;
             }
         }
+    }
+    return PGX_OK;
+}
+
+/* the checks of one pgx_sde_actor_action_log_prob launch, device and host alike */
+int pgx_sde_actor_lp_check_launch(const pgx_sde_actor_config* c, const pgx_sde_actor_lp_io* io, int32_t B,
+                                  const char* what) {
+    return check_lp_io(io, B, c->obs_dim, what);
+}
+
+extern "C" int pgx_sde_actor_log_prob_host(const pgx_sde_actor_config* cfg, const pgx_sde_actor_weights* w,
+                                           const float* std_ha, const float* exploration_mat,
+                                           const pgx_sde_actor_lp_io* io, int32_t n) {
+    const char* what = "pgx_sde_actor_log_prob_host";
+    int rc = pgx_sde_actor_check_config(cfg, what, false);
+    if (rc == PGX_OK) rc = pgx_sde_actor_lp_check_launch(cfg, io, n, what);
+    if (rc != PGX_OK) return rc;
+    if (!exploration_mat) return bad(what, "null exploration_mat");
+    if (!w) return bad(what, "null weights");
+    const int nl = cfg->n_layers, A = cfg->action_dim, od = cfg->obs_dim, H = cfg->hidden[nl - 1];
+    for (int l = 0; l <= nl; l++)
+        if (!w->weight[l] || !w->bias[l]) return bad(what, "null weight or bias pointer");
+    if (!std_ha && !w->log_std) return bad(what, "null std and log_std");
+    const int K16 = (H + 15) & ~15;
+    std::vector<float> std2((size_t)H * A);
+    for (size_t j = 0; j < std2.size(); j++) {
+        const float s = std_ha ? std_ha[j] : std::exp(w->log_std[j]);
+        std2[j] = s * s;
+    }
+    const float clip = (float)cfg->clip_mean;
+    std::vector<float> x(od + 6), y(PGX_ACTOR_MAX_WIDTH), z(PGX_ACTOR_MAX_WIDTH);
+    for (int32_t b = 0; b < n; b++) {
+        stage_x_rows(x.data(), io, (size_t)b, od);
+        const float* latent = hidden_layers(nl, cfg->hidden, w->weight, w->bias, x.data(), od + 6, y.data(), z.data());
+        if (io->latent_out)
+            for (int h = 0; h < H; h++) io->latent_out[(size_t)b * H + h] = latent[h];
+        float mu[PGX_ACTOR_MAX_ACTION], lp[PGX_ACTOR_MAX_ACTION], c[PGX_ACTOR_MAX_ACTION];
+        linear(w->weight[nl], w->bias[nl], latent, H, A, false, mu);
+        for (int d = 0; d < A; d++) {
+            float noise = 0.0f, var = 0.0f;   /* the Linear chain with bias +0, padded to K16 */
+            for (int h = 0; h < H; h++) {
+                noise = std::fmaf(latent[h], exploration_mat[(size_t)h * A + d], noise);
+                const float sq = latent[h] * latent[h];
+                var = std::fmaf(sq, std2[(size_t)h * A + d], var);
+            }
+            for (int h = H; h < K16; h++) {
+                noise = std::fmaf(0.0f, 0.0f, noise);
+                var = std::fmaf(0.0f, 0.0f, var);
+            }
+            const size_t o = (size_t)b * A + d;
+            const float mean = clip_to(mu[d], clip);
+            float act, g;
+            sde_lp_terms(mean, noise, var, &act, &g, &lp[d], &c[d]);
+            io->action[o] = act;
+            if (io->mean_out) io->mean_out[o] = mean;
+            if (io->noise_out) io->noise_out[o] = noise;
+            if (io->variance_out) io->variance_out[o] = var;
+            if (io->gaussian_action_out) io->gaussian_action_out[o] = g;
+        }
+        io->log_prob[b] = sum_log_prob(lp, c, A);
     }
     return PGX_OK;
 }

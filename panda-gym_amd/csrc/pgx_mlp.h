@@ -1,6 +1,7 @@
 /*
  * pgx_mlp.h -- the device side the policy units (pgx_actor.hip, pgx_actor_critic.hip, pgx_sde_actor.hip,
- * pgx_quantile_critic.hip) share: the plan of one stack of Linears, the feature staging their forward kernels open with, one
+ * pgx_quantile_critic.hip) share: the plan of one stack of Linears, the feature staging their forward kernels open with
+ * (dense per env, or through row strides for a batch), the ordered sums of a batch row's log-probability, one
  * Linear over a workgroup's env tile as v_mfma_f32_16x16x4_f32 on activations kept in LDS, the loop that
  * runs a stack through two LDS regions, the Gaussian draw from the Philox stream, the advance of a
  * device-resident noise word, and the kernel that packs torch-layout weights for the Linear.  Arithmetic
@@ -49,6 +50,46 @@ __device__ __forceinline__ void stage_features(float* lds, const float* obs, con
             else v = obs[(size_t)e * od + (k - 6)];
         }
         lds[r * S + k] = v;
+    }
+}
+
+/* the same for the rows of a batch, each field read through its own row stride (floats): a HER batch's
+ * rows are read where they lie */
+template <int MT>
+__device__ __forceinline__ void stage_features_rows(float* lds, const float* obs, const float* achieved_goal,
+                                                    const float* desired_goal, int s_obs, int s_ag, int s_dg, int row0,
+                                                    int B, int od, int K0, int S, int tid) {
+    const int in_dim = od + 6;
+    for (int idx = tid; idx < MT * 16 * K0; idx += THREADS) {
+        const int r = idx / K0, k = idx - r * K0;
+        const size_t b = (size_t)(row0 + r);
+        float v = 0.0f;
+        if (row0 + r < B && k < in_dim) {
+            if (k < 3) v = achieved_goal[b * s_ag + k];
+            else if (k < 6) v = desired_goal[b * s_dg + (k - 3)];
+            else v = obs[b * s_obs + (k - 6)];
+        }
+        lds[r * S + k] = v;
+    }
+}
+
+/* The sums of a batch row's log-probability, log_prob[b] = (lp_0 + lp_1 + ...) - (c_0 + c_1 + ...), each
+ * from its first term in ascending d: thread (row r = tid / 8, dimension d = tid % 8) hands in its two
+ * terms, the thread of d = 0 adds them up and stores.  sh: 512 floats of LDS.  Every thread of the
+ * workgroup calls this (one barrier inside). */
+__device__ __forceinline__ void sum_log_prob(float* sh, float lp, float c, bool own, int A, float* log_prob, size_t b,
+                                             int tid) {
+#pragma clang fp contract(off)
+    sh[2 * tid] = lp;
+    sh[2 * tid + 1] = c;
+    __syncthreads();
+    if (own && (tid & 7) == 0) {
+        float s_lp = sh[2 * tid], s_c = sh[2 * tid + 1];
+        for (int d = 1; d < A; d++) {
+            s_lp = s_lp + sh[2 * (tid + d)];
+            s_c = s_c + sh[2 * (tid + d) + 1];
+        }
+        log_prob[b] = s_lp - s_c;
     }
 }
 

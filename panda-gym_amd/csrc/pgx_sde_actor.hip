@@ -18,10 +18,22 @@
  * i < A) -- and draws block q = (h block) A + i of that env, whose four flat indices 4 q .. 4 q + 3
  * are, transposed, exactly the 4 A floats of that env's h block.  The A lanes of one (env, h block)
  * exchange them through LDS, so every lane stores the one contiguous 16 bytes it owns.
+ *
+ * Log-probability kernel (pgx_sde_actor_action_log_prob, SB3's actor.action_log_prob as TQC.train reaches
+ * it): the forward's workgroup over a tile of 32 batch rows (16 for a batch of up to 16, or where 32 do
+ * not fit the LDS), read through their row strides.  The noise of a batch comes from ONE shared matrix Eb
+ * [H, A], kept plain and packed into rows 8..14 of mu's tile, so the head tile's MFMAs give mean and noise
+ * together; the latent is then squared in place and a second tile, std2 = std * std packed at
+ * set_weights, gives the variance over the squares.  The epilogue (the inverse of the squash, the Gaussian
+ * density, the correction) runs with contraction off, one thread per (row, dimension), and the sums go
+ * through the dead activations.  pgx_sde_actor_reset_batch_noise draws Eb with a generation word and a
+ * counter tag of its own; the per-env matrices never see any of this.
  */
 #include "pgx_policy.h"   /* pgx_mlp.h, pgx_common.h, include/pgx.h */
 
-int pgx_sde_actor_check_config(const pgx_sde_actor_config* c, const char* what, bool with_envs);  /* pgx_actor_host.cpp */
+/* pgx_actor_host.cpp */
+int pgx_sde_actor_check_config(const pgx_sde_actor_config* c, const char* what, bool with_envs);
+int pgx_sde_actor_lp_check_launch(const pgx_sde_actor_config* c, const pgx_sde_actor_lp_io* io, int32_t B, const char* what);
 
 namespace {
 
@@ -38,6 +50,21 @@ struct SdeArgs {
     unsigned long long* gen;
     uint32_t* ticket;
 };
+
+/* what the batch entries use beside SdeArgs: the shared matrix Eb and std2, plain [H, A] and packed */
+struct SdeBatch {
+    float* Eb;                 /* [H, A] */
+    float* std2;               /* [H, A] */
+    float* Pmu;                /* mu's packed tile: Eb goes to its rows 8..14 */
+    float* P2;                 /* std2's packed tile (rows 0..6), its 16 bias floats (+0) behind it */
+    unsigned long long* gen;
+    uint32_t* ticket;
+};
+
+/* element (output row, k) of a packed Linear of one tile: pgx_mlp.h's pack_kernel with ntiles = 1 */
+__device__ __forceinline__ int packed_index(int row, int k) {
+    return (((k >> 4) * 64) + (k & 3) * 16 + row) * 4 + ((k >> 2) & 3);
+}
 
 /* the epilogue, every operation rounded on its own */
 __device__ __forceinline__ float squash(float mean, float noise, bool deterministic) {
@@ -114,6 +141,126 @@ __global__ __launch_bounds__(THREADS) void sde_forward_kernel(SdeArgs a, pgx_sde
         }
 }
 
+/* the log-probability epilogue of one (row, dimension), every operation rounded on its own */
+__device__ __forceinline__ void sde_lp_terms(float mean, float noise, float var, float* act, float* gp, float* lp, float* c) {
+#pragma clang fp contract(off)
+    const float scale = sqrtf(var + 1e-6f);
+    const float a = tanhf(mean + noise);
+    const float lim = 1.0f - 1.1920929e-7f;
+    const float x = a < -lim ? -lim : (a > lim ? lim : a);
+    const float g = 0.5f * (log1pf(x) - log1pf(-x));
+    const float z = g - mean;
+    *lp = ((-(z * z)) / (2.0f * (scale * scale)) - logf(scale)) - 0.9189385f;
+    const float t = tanhf(g);
+    *c = logf((1.0f - t * t) + 1e-6f);
+    *act = a;
+    *gp = g;
+}
+
+/* pgx_sde_actor_action_log_prob: the forward's workgroup over a tile of batch rows read through their
+ * strides (a.n is the batch size).  Behind the trunk the head tile gives mean (rows 0..6) and the noise
+ * chain against Eb (rows 8..14); their owners take them into registers, the latent is squared in place,
+ * and std2's tile over the squares gives the variance where the head tile lay. */
+template <int MT>
+__global__ __launch_bounds__(THREADS) void sde_lp_kernel(SdeArgs a, SdeBatch bt, pgx_sde_actor_lp_io io) {
+    extern __shared__ float lds[];
+    constexpr int ROWS = MT * 16;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int S = a.S, B = a.n, A = a.ad, H = a.H;
+    const int row0 = blockIdx.x * ROWS;
+    stage_features_rows<MT>(lds, io.obs, io.achieved_goal, io.desired_goal, io.obs_stride, io.achieved_goal_stride,
+                            io.desired_goal_stride, row0, B, a.od, a.plan.nkb[0] * 16, S, tid);
+    __syncthreads();
+    const int lm = a.plan.n_linear - 1;
+    const int in_off = run_linears<MT>(lds, a.params, a.plan, lm, true, 0, S, ROWS * S, 0, S, lane, wave);
+    const int out_off = in_off == 0 ? ROWS * S : 0;
+    const int nkb = a.plan.nkb[lm];
+    linear_layer<MT>(lds, in_off, out_off, a.params + a.plan.woff[lm], a.params + a.plan.boff[lm], nkb, 1, S, false, lane,
+                     wave);
+    __syncthreads();
+    const int r = tid >> 3, d = tid & 7;
+    const int b = row0 + r;
+    const bool own = r < ROWS && d < A && b < B;
+    float mean = 0.0f, noise = 0.0f;
+    if (own) {
+        mean = lds[out_off + r * S + d];
+        if (a.clip > 0.0f) mean = mean < -a.clip ? -a.clip : (mean > a.clip ? a.clip : mean);
+        noise = lds[out_off + r * S + 8 + d];
+    }
+    const int K16 = nkb * 16;
+    for (int idx = tid; idx < ROWS * K16; idx += THREADS) {
+        const int rr = idx / K16, h = idx - rr * K16;
+        const float v = lds[in_off + rr * S + h];
+        if (io.latent_out && h < H && row0 + rr < B) io.latent_out[(size_t)(row0 + rr) * H + h] = v;
+        lds[in_off + rr * S + h] = v * v;
+    }
+    __syncthreads();
+    linear_layer<MT>(lds, in_off, out_off, bt.P2, bt.P2 + nkb * 256, nkb, 1, S, false, lane, wave);
+    __syncthreads();
+    float lp = 0.0f, c = 0.0f;
+    if (own) {
+        const float var = lds[out_off + r * S + d];
+        float act, g;
+        sde_lp_terms(mean, noise, var, &act, &g, &lp, &c);
+        const size_t o = (size_t)b * A + d;
+        io.action[o] = act;
+        if (io.mean_out) io.mean_out[o] = mean;
+        if (io.noise_out) io.noise_out[o] = noise;
+        if (io.variance_out) io.variance_out[o] = var;
+        if (io.gaussian_action_out) io.gaussian_action_out[o] = g;
+    }
+    __syncthreads();   /* the variance tile is read: the activations are dead and carry the sums' terms */
+    sum_log_prob(lds, lp, c, own, A, io.log_prob, (size_t)b, tid);
+}
+
+/* pgx_sde_actor_reset_batch_noise: thread q of the grid draws block q of the shared matrix, flat indices
+ * 4 q .. 4 q + 3, and stores each both plain and where mu's packed tile holds it */
+__global__ __launch_bounds__(THREADS) void sde_batch_reset_kernel(SdeArgs a, SdeBatch bt, float* eps_out) {
+    __shared__ unsigned long long sh_gen;
+    const int tid = threadIdx.x;
+    load_word(&sh_gen, bt.gen, true, tid);
+    __syncthreads();
+    const int q = blockIdx.x * THREADS + tid, HA = a.H * a.ad;
+    if (4 * q < HA) {
+        const unsigned long long gen = sh_gen;
+        uint32_t rr[4];
+        philox((uint32_t)gen, (uint32_t)(gen >> 32), 0u, PGX_SDE_BATCH_PHILOX_TAG ^ (uint32_t)q, a.seed_lo, a.seed_hi, rr);
+        float eps[4];
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            float rad, ang;
+            box_muller(rr[2 * c], rr[2 * c + 1], &rad, &ang);
+            eps[2 * c] = rad * cosf(ang);
+            eps[2 * c + 1] = rad * sinf(ang);
+        }
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const int j = 4 * q + c;
+            if (j >= HA) break;
+            const int h = j / a.ad, d = j - h * a.ad;
+            const float v = eps[c] * a.std[j];
+            bt.Eb[j] = v;
+            bt.Pmu[packed_index(8 + d, h)] = v;
+            if (eps_out) eps_out[j] = eps[c];
+        }
+    }
+    advance_word(bt.gen, bt.ticket, &sh_gen, gridDim.x, true, tid);
+}
+
+/* the shared matrix from SB3's [H, A] (in != NULL: plain and packed), or into it */
+__global__ __launch_bounds__(256) void sde_batch_copy_kernel(SdeArgs a, SdeBatch bt, const float* in, float* out) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= a.H * a.ad) return;
+    if (in) {
+        const int h = j / a.ad, d = j - h * a.ad;
+        const float v = in[j];
+        bt.Eb[j] = v;
+        bt.Pmu[packed_index(8 + d, h)] = v;
+    } else {
+        out[j] = bt.Eb[j];
+    }
+}
+
 /* blockDim.x = 16 A KB: KB whole h blocks of one tile of 16 envs; grid (ceil(H4 / KB), tiles) */
 __global__ __launch_bounds__(THREADS) void sde_reset_kernel(SdeArgs a, int KB, float* eps_out, uint32_t* philox_out) {
     __shared__ float sh[THREADS * 4];
@@ -177,12 +324,22 @@ __global__ __launch_bounds__(256) void sde_translate_kernel(SdeArgs a, float* pl
     else plain[idx] = a.E[s];
 }
 
-/* std = expf(log_std), or (out != NULL) a copy of std */
-__global__ __launch_bounds__(256) void sde_std_kernel(const float* log_std, float* std, float* out, int n) {
+/* std = expf(log_std) and std2 = std * std (plain and packed: A the action dimension), or (out != NULL) a
+ * copy of std */
+__global__ __launch_bounds__(256) void sde_std_kernel(const float* log_std, float* std, float* out, int n, float* std2,
+                                                      float* P2, int A) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= n) return;
-    if (out) out[idx] = std[idx];
-    else std[idx] = expf(log_std[idx]);
+    if (out) {
+        out[idx] = std[idx];
+        return;
+    }
+    const float s = expf(log_std[idx]);
+    const float s2 = s * s;
+    const int h = idx / A;
+    std[idx] = s;
+    std2[idx] = s2;
+    P2[packed_index(idx - h * A, h)] = s2;
 }
 
 }  // namespace
@@ -197,6 +354,13 @@ struct pgx_sde_actor {
     int mt;                     /* env tiles of 16 per workgroup */
     int kb;                     /* h blocks per reset workgroup */
     size_t lds_bytes;
+    SdeBatch bt;
+
+    size_t lds_need(int mt) const { return 2 * (size_t)mt * 16 * a.S * 4; }
+    /* row tiles of 16 per workgroup of a batch launch: 32 rows from 17 on, where they fit the LDS */
+    int lp_tile(int B) const {
+        return choose_tile(B, "PGX_SDE_LP_TILE", [this](int mt) { return lds_need(mt); }, 17);
+    }
 };
 
 extern "C" {
@@ -235,10 +399,13 @@ int pgx_sde_actor_create(const pgx_sde_actor_config* cfg, int device, pgx_sde_ac
     h->lds_bytes = lds_need(h->mt);
     h->kb = THREADS / (16 * a.ad);
     const size_t tiles = ((size_t)cfg->n_envs + 15) / 16;
-    const size_t bytes[5] = {n_params * 4, n_plain * 4, n_std * 4, tiles * a.H4 * 16 * a.ad * 4 * 4, 256};
-    void* ptr[5];
+    /* the last region: std2's packed tile and bias, then Eb and std2 plain */
+    const size_t n_p2 = (size_t)a.plan.nkb[nl] * 256 + 16;
+    const size_t bytes[6] = {n_params * 4, n_plain * 4, n_std * 4, tiles * a.H4 * 16 * a.ad * 4 * 4, 256,
+                             (n_p2 + 2 * n_std) * 4};
+    void* ptr[6];
     const void* fn = h->mt == 2 ? (const void*)sde_forward_kernel<2> : (const void*)sde_forward_kernel<1>;
-    rc = create_blob("pgx_sde_actor_create", device, bytes, 5, ptr, {fn}, h->lds_bytes);
+    rc = create_blob("pgx_sde_actor_create", device, bytes, 6, ptr, {fn}, h->lds_bytes);
     if (rc != PGX_OK) {
         delete h;
         return rc;
@@ -249,6 +416,23 @@ int pgx_sde_actor_create(const pgx_sde_actor_config* cfg, int device, pgx_sde_ac
     a.E = (float*)ptr[3];
     a.gen = (unsigned long long*)ptr[4];
     a.ticket = (uint32_t*)((char*)ptr[4] + 8);
+    h->bt.gen = (unsigned long long*)((char*)ptr[4] + 16);
+    h->bt.ticket = (uint32_t*)((char*)ptr[4] + 24);
+    h->bt.Pmu = h->params + a.plan.woff[nl];
+    h->bt.P2 = (float*)ptr[5];
+    h->bt.Eb = h->bt.P2 + n_p2;
+    h->bt.std2 = h->bt.Eb + n_std;
+    /* the batch kernels' dynamic LDS: 16 rows always fit, 32 where they do */
+    bool ok = hipFuncSetAttribute((const void*)sde_lp_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)h->lds_need(1)) == hipSuccess;
+    if (choose_tile(17, nullptr, [h](int mt) { return h->lds_need(mt); }, 17) == 2)
+        ok = ok && hipFuncSetAttribute((const void*)sde_lp_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)h->lds_need(2)) == hipSuccess;
+    if (!ok) {
+        (void)hipFree(h->params);
+        delete h;
+        return pgx_set_error(PGX_E_HIP, "pgx_sde_actor_create: device setup failed");
+    }
     *out = h;
     return PGX_OK;
 }
@@ -281,7 +465,7 @@ int pgx_sde_actor_set_weights(pgx_sde_actor_handle h, const pgx_sde_actor_weight
     if (hipMemcpyAsync(ls, w->log_std, (size_t)n_std * 4, hipMemcpyDefault, st) != hipSuccess)
         return pgx_set_error(PGX_E_HIP, "pgx_sde_actor_set_weights: copy failed");
     hipLaunchKernelGGL(sde_std_kernel, dim3((n_std + 255) / 256), dim3(256), 0, st, (const float*)ls, h->a.std,
-                       (float*)nullptr, n_std);
+                       (float*)nullptr, n_std, h->bt.std2, h->bt.P2, h->a.ad);
     return hipGetLastError() == hipSuccess ? PGX_OK : pgx_set_error(PGX_E_HIP, "pgx_sde_actor_set_weights: launch failed");
 }
 
@@ -300,6 +484,54 @@ int pgx_sde_actor_forward(pgx_sde_actor_handle h, const pgx_sde_actor_io* io, in
     launch_tiles(sde_forward_kernel<1>, sde_forward_kernel<2>, h->mt, h->a.n, h->lds_bytes, stream, h->a, *io,
                  deterministic);
     return hipGetLastError() == hipSuccess ? PGX_OK : pgx_set_error(PGX_E_HIP, "pgx_sde_actor_forward: launch failed");
+}
+
+int pgx_sde_actor_action_log_prob(pgx_sde_actor_handle h, const pgx_sde_actor_lp_io* io, int32_t B, void* stream) {
+    const char* what = "pgx_sde_actor_action_log_prob";
+    if (!h) return fail(PGX_E_INVALID, what, "null handle");
+    const int rc = pgx_sde_actor_lp_check_launch(&h->cfg, io, B, what);
+    if (rc != PGX_OK) return rc;
+    SdeArgs a = h->a;
+    a.n = B;
+    const int mt = h->lp_tile(B);
+    launch_tiles(sde_lp_kernel<1>, sde_lp_kernel<2>, mt, B, h->lds_need(mt), stream, a, h->bt, *io);
+    return hipGetLastError() == hipSuccess ? PGX_OK : fail(PGX_E_HIP, what, "launch failed");
+}
+
+int pgx_sde_actor_reset_batch_noise(pgx_sde_actor_handle h, float* eps_out, void* stream) {
+    const char* what = "pgx_sde_actor_reset_batch_noise";
+    if (!h) return fail(PGX_E_INVALID, what, "null handle");
+    const int nq = (h->a.H * h->a.ad + 3) / 4;
+    hipLaunchKernelGGL(sde_batch_reset_kernel, dim3((nq + THREADS - 1) / THREADS), dim3(THREADS), 0, (hipStream_t)stream,
+                       h->a, h->bt, eps_out);
+    return hipGetLastError() == hipSuccess ? PGX_OK : fail(PGX_E_HIP, what, "launch failed");
+}
+
+int pgx_sde_actor_get_batch_matrix(pgx_sde_actor_handle h, float* out, void* stream) {
+    const char* what = "pgx_sde_actor_get_batch_matrix";
+    if (!h || !out) return fail(PGX_E_INVALID, what, "null handle or out pointer");
+    hipLaunchKernelGGL(sde_batch_copy_kernel, dim3((h->a.H * h->a.ad + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->a,
+                       h->bt, (const float*)nullptr, out);
+    return hipGetLastError() == hipSuccess ? PGX_OK : fail(PGX_E_HIP, what, "launch failed");
+}
+
+int pgx_sde_actor_set_batch_matrix(pgx_sde_actor_handle h, const float* in, void* stream) {
+    const char* what = "pgx_sde_actor_set_batch_matrix";
+    if (!h || !in) return fail(PGX_E_INVALID, what, "null handle or in pointer");
+    hipLaunchKernelGGL(sde_batch_copy_kernel, dim3((h->a.H * h->a.ad + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->a,
+                       h->bt, in, (float*)nullptr);
+    return hipGetLastError() == hipSuccess ? PGX_OK : fail(PGX_E_HIP, what, "launch failed");
+}
+
+int pgx_sde_actor_batch_state(pgx_sde_actor_handle h, uint64_t* generation, void* stream) {
+    if (!h || !generation)
+        return pgx_set_error(PGX_E_INVALID, "pgx_sde_actor_batch_state: null handle or generation pointer");
+    return read_word("pgx_sde_actor_batch_state", h->bt.gen, generation, stream);
+}
+
+int pgx_sde_actor_batch_set_state(pgx_sde_actor_handle h, uint64_t generation, void* stream) {
+    if (!h) return pgx_set_error(PGX_E_INVALID, "pgx_sde_actor_batch_set_state: null handle");
+    return write_word("pgx_sde_actor_batch_set_state", h->bt.gen, generation, stream);
 }
 
 int pgx_sde_actor_state(pgx_sde_actor_handle h, uint64_t* generation, void* stream) {
@@ -332,7 +564,7 @@ int pgx_sde_actor_get_std(pgx_sde_actor_handle h, float* out, void* stream) {
     if (!h || !out) return pgx_set_error(PGX_E_INVALID, "pgx_sde_actor_get_std: null handle or out pointer");
     const int n_std = h->a.H * h->a.ad;
     hipLaunchKernelGGL(sde_std_kernel, dim3((n_std + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)nullptr,
-                       h->a.std, out, n_std);
+                       h->a.std, out, n_std, (float*)nullptr, (float*)nullptr, h->a.ad);
     return hipGetLastError() == hipSuccess ? PGX_OK : pgx_set_error(PGX_E_HIP, "pgx_sde_actor_get_std: launch failed");
 }
 

@@ -13,8 +13,10 @@ fallback: with ``device="cpu"`` a ``QuantileCritic`` only holds and maps paramet
 ``state_dict`` / ``forward_host`` / ``td_target_host``, the host models of the kernels' arithmetic, which
 are test oracles).
 
-Not here: gradients, the quantile Huber loss, the actor loss's Q mean, an action log-probability from the
-device actors (``next_actions`` and ``next_log_prob`` are the caller's buffers), optimisers.
+``next_actions`` and ``next_log_prob`` are the caller's buffers: ``Actor.action_log_prob_rows`` /
+``SdeActor.action_log_prob_rows`` fill them from the same batch in one launch (actor.py, sde_actor.py).
+
+Not here: gradients, the quantile Huber loss, the actor loss's Q mean, optimisers.
 """
 from __future__ import annotations
 
@@ -161,21 +163,6 @@ class QuantileCritic(Policy):
             self._loading = SETS
 
     # --------------------------------------------------------------- launches
-    def _field(self, x, width: int, B: Optional[int], name: str):
-        """A row-indexed input as (tensor, row stride in floats): a device f32 tensor [B, width] (or [B] for
-        width 1) whose rows are contiguous is read in place, whatever its row stride; anything else is
-        copied to a dense one."""
-        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-        if t.dim() == 1 and width == 1:
-            t = t.unsqueeze(1)
-        if t.dim() != 2 or t.shape[1] != width or (B is not None and t.shape[0] != B):
-            raise ValueError(f"{name}: expected shape [{'B' if B is None else B}, {width}], got {list(t.shape)}")
-        ok = t.dtype == torch.float32 and t.device == self.device and (width == 1 or t.stride(1) == 1) \
-            and (t.shape[0] == 1 or t.stride(0) >= width)
-        if not ok:
-            t = t.to(device=self.device, dtype=torch.float32).contiguous()
-        return t, (width if t.shape[0] == 1 else int(t.stride(0)))
-
     def _io(self, obs: Dict[str, Any], actions, B: Optional[int] = None):
         o, so = self._field(obs["observation"], self.obs_dim, B, "observation")
         B = int(o.shape[0])

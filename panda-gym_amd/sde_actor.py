@@ -13,7 +13,13 @@ new matrices.  ``full_std=True``, ``use_expln=False`` and ``latent_sde = latent_
 what is built.  No CPU fallback: with ``device="cpu"`` an ``SdeActor`` only holds and maps parameters
 (``load_state_dict`` / ``state_dict`` / ``forward_host``, the host model of the kernel's arithmetic).
 
-The distribution's variance and ``log_prob``, critics and optimisers are training-side and not here.
+``action_log_prob`` is SB3's ``actor.action_log_prob(observations)`` as ``TQC.train`` reaches it: for a batch
+of any size, with the noise of the ONE shared ``exploration_mat`` [H, A] (``reset_batch_noise``; SB3's
+``get_noise`` takes it when the batch length differs from the number of per-env matrices), the
+distribution's variance, the inverse of the squash and the log-probability with its correction, in one
+launch that reads a HER batch's rows in place (``action_log_prob_rows``).
+
+Gradients and optimisers are training-side and not here; the critics are in quantile_critic.py.
 """
 from __future__ import annotations
 
@@ -180,6 +186,103 @@ class SdeActor(Policy):
                        abi.ptr(o["achieved_goal"]), abi.ptr(o["desired_goal"]), abi.ptr(m), n, abi.ptr(mean),
                        abi.ptr(latent), abi.ptr(noise))
         return mean, latent, noise
+
+    # ------------------------------------------------- action log-probability
+    _LP_PHILOX = False
+
+    def _lp_planes(self) -> Dict[str, int]:
+        A, H = self.action_dim, max(self.latent_dim, 0)
+        return {"mean": A, "latent": H, "noise": A, "variance": A, "gaussian_action": A}
+
+    def reset_batch_noise(self, eps_out: Optional["torch.Tensor"] = None) -> None:
+        """Resample the one exploration matrix the batch entry uses (SB3 ``actor.reset_noise()`` at the top of
+        a gradient step): one launch, which moves ``batch_noise_generation`` on by one.  The per-env
+        matrices and ``noise_generation`` are not touched.  ``eps_out`` (debug): a contiguous device f32 [H,
+        A] tensor that receives the standard normal draw."""
+        self._need_device()
+        e = None
+        if eps_out is not None:
+            if eps_out.dtype != torch.float32 or eps_out.device != self.device or not eps_out.is_contiguous() \
+                    or tuple(eps_out.shape) != (self.latent_dim, self.action_dim):
+                raise ValueError(f"eps_out must be a contiguous f32 [{self.latent_dim}, {self.action_dim}] tensor on "
+                                 f"{self.device}")
+            e = C.c_void_p(eps_out.data_ptr())
+        self._call("reset_batch_noise", self._h, e, self._stream())
+
+    def _get_batch_word(self) -> int:
+        self._need_device()
+        v = C.c_uint64(0)
+        self._call("batch_state", self._h, C.byref(v), self._stream())
+        return int(v.value)
+
+    def _set_batch_word(self, value: int) -> None:
+        self._need_device()
+        self._call("batch_set_state", self._h, C.c_uint64(int(value) & 0xFFFFFFFFFFFFFFFF), self._stream())
+
+    batch_noise_generation = property(_get_batch_word, _set_batch_word, doc="""The device word that keys the draw
+        of ``exploration_mat`` and counts ``reset_batch_noise`` (this synchronises); ``noise_generation`` is
+        another word.  Setting it back reproduces the draws.""")
+
+    @property
+    def exploration_mat(self) -> "torch.Tensor":
+        """The shared matrix [H, A] of the batch entry, SB3's ``exploration_mat`` (a copy).  Device only."""
+        self._need_device()
+        out = torch.empty((self.latent_dim, self.action_dim), dtype=torch.float32, device=self.device)
+        self._call("get_batch_matrix", self._h, C.c_void_p(out.data_ptr()), self._stream())
+        return out
+
+    @exploration_mat.setter
+    def exploration_mat(self, value: Any) -> None:
+        self._need_device()
+        t = self._dev(value, (self.latent_dim, self.action_dim))
+        self._call("set_batch_matrix", self._h, C.c_void_p(t.data_ptr()), self._stream())
+        self._keep_b = t   # alive until the stream has consumed it
+
+    def action_log_prob(self, obs: Dict[str, Any], out=None):
+        """SB3's ``actor.action_log_prob(obs)`` on the gSDE distribution as ``TQC.train`` reaches it: ``(actions
+        [B, A], log_prob [B])`` of a batch of any size ``B`` with the noise of the one ``exploration_mat``, one
+        launch.  ``obs``: an observation dict of [B, .] tensors; device f32 tensors with contiguous rows,
+        views into a HER batch's rows included, are read in place.  ``out``: a pair of contiguous f32
+        tensors [B, A] and [B] to fill (returned as they are)."""
+        self._need_device()
+        io = abi.PgxSdeActorLpIo()
+        B, act, lp, keep = self._lp_io(io, obs, out)
+        self._lp_debug_into(io, B)
+        check(self.lib.pgx_sde_actor_action_log_prob(self._h, C.byref(io), B, self._stream()),
+              "pgx_sde_actor_action_log_prob", self.lib)
+        self._keep = keep + [act, lp]   # alive until the stream has consumed them
+        return act, lp
+
+    def action_log_prob_rows(self, batch: Dict[str, "torch.Tensor"], next: bool = True, out=None):
+        """``action_log_prob`` on a HER batch (``buf.alloc_batch`` / ``buf.sample_into``): ``next_obs``,
+        ``next_achieved_goal`` and ``next_desired_goal`` (``next=False``: ``obs``, ``achieved_goal``,
+        ``desired_goal``) are read from ``batch["rows"]`` in place."""
+        return self.action_log_prob(self._batch_obs(batch, next), out=out)
+
+    def log_prob_host(self, obs: Dict[str, Any], exploration_mat: Any, std: Any = None) -> Dict[str, np.ndarray]:
+        """The library's host model of ``action_log_prob`` for any number of rows: ``action``, ``log_prob`` and
+        the planes ``mean``, ``latent``, ``noise``, ``variance``, ``gaussian_action`` as numpy f32.  ``std`` [H,
+        A]: what the variance is built from -- by default the handle's (``self.std``), on a CPU actor the host
+        libm's ``exp(log_std)``.  The planes but ``gaussian_action`` are what the kernel gives bit for bit.  A
+        test oracle."""
+        ws, bs = self._host_params()
+        H, A = max(self.latent_dim, 0), self.action_dim
+        f = lambda x: np.ascontiguousarray(x.cpu().numpy() if torch.is_tensor(x) else x, dtype=np.float32)  # noqa: E731
+        m = f(exploration_mat)
+        if m.shape != (H, A):
+            raise ValueError(f"expected exploration_mat of shape {[H, A]}, got {list(m.shape)}")
+        if std is None and self._h is not None:
+            std = self.std
+        s = None if std is None else f(std)
+        if s is not None and s.shape != (H, A):
+            raise ValueError(f"expected std of shape {[H, A]}, got {list(s.shape)}")
+        ls = np.ascontiguousarray(self._log_std.cpu().numpy())
+        w = self._weights_struct([x.ctypes.data for x in ws], [x.ctypes.data for x in bs], ls.ctypes.data)
+        io = abi.PgxSdeActorLpIo()
+        n, res = self._host_lp_io(io, obs, self._lp_planes())
+        self._call("log_prob_host", C.byref(self._cfg), C.byref(w), abi.ptr(s), abi.ptr(m), C.byref(io), n)
+        del res["_keep"]
+        return res
 
     # --------------------------------------------------------------- rollouts
     def _venv_obs(self, venv) -> Dict[str, "torch.Tensor"]:
