@@ -1416,8 +1416,8 @@ int pgx_sde_actor_log_prob_host(const pgx_sde_actor_config* cfg, const pgx_sde_a
 /* ----------------------------------------------------------------------
  * QuantileCritic: sb3_contrib TQC's quantile critics on the device (pgx_quantile_critic.hip): the
  * forward of `critic` or `critic_target` (tqc/policies.py, Critic.forward), the no_grad block of
- * TQC.train that builds the truncated TD target (tqc/tqc.py) as one launch, and the Polyak step.  No
- * gradient is computed here.  This is a restatement: neither library is importable where this is built,
+ * TQC.train that builds the truncated TD target (tqc/tqc.py) as one launch, and the Polyak step.  The
+ * critic loss, its gradient and Adam: "the critic update", further down.  This is a restatement: neither library is importable where this is built,
  * parity against them is not pinned by a test.
  *
  * Networks: n_critics independent nets qf0 .. qf{n-1}; each n_layers x (Linear + ReLU), widths
@@ -1560,6 +1560,115 @@ int pgx_qc_sync_target(pgx_qc_handle h, void* stream);
 int pgx_qc_forward_host(const pgx_qc_config* cfg, const pgx_qc_weights* w, const pgx_qc_io* io, int32_t B);
 int pgx_qc_target_host(const pgx_qc_config* cfg, const pgx_qc_weights* w, const pgx_qc_io* io, int32_t B,
                        int32_t n_target);
+
+/* ----------------------------------------------------------------------
+ * QuantileCritic, the critic update: TQC.train's critic loss, its gradient with respect to every
+ * parameter of the ONLINE set, and torch.optim.Adam's step on them (pgx_quantile_critic.hip).  A
+ * restatement of sb3_contrib (tqc.py: critic_loss = quantile_huber_loss(current_quantiles,
+ * target_quantiles, sum_over_quantiles=False); critic.optimizer.zero_grad(); critic_loss.backward();
+ * critic.optimizer.step()) and of torch's Adam; parity with either is held to fp64 by the tests, not
+ * pinned bit for bit.  The actor loss, the ent_coef loss, dQ/d(action) and gradient clipping are not here.
+ *
+ * Loss.  q[b][c][j]: the ONLINE set's quantiles of row b, bit for bit pgx_qc_forward's.  t[b][k], k <
+ * n_target: target_quantiles.  n_q = n_quantiles.  In f32, every operation rounded on its own but the
+ * named fmaf:
+ *     tau_j = ((float)j + 0.5f) / (float)n_q
+ *     d     = t[b][k] - q[b][c][j]
+ *     w     = fabsf(tau_j - (d < 0 ? 1.0f : 0.0f))
+ *     huber = fabsf(d) > 1.0f ? fabsf(d) - 0.5f : (d * d) * 0.5f
+ *     clamp = d < -1.0f ? -1.0f : (d > 1.0f ? 1.0f : d)
+ *     lt[b][c][j] = chain over k = 0 .. n_target - 1 ascending from +0: acc = fmaf(w, huber, acc)
+ *     gs[b][c][j] = chain over k = 0 .. n_target - 1 ascending from +0: acc = fmaf(w, clamp, acc)
+ *     inv_count = 1.0f / (float)(B * n_critics * n_q * n_target)     (the product as a 64-bit integer)
+ *     dq[b][c][j] = (-inv_count) * gs[b][c][j]
+ *     rl[b] = sum from +0 of lt[b][c][j] in ascending flat index c * n_q + j, one addition per term
+ *     seg[i] = sum from +0 of rl[b], b = 64 i .. min(64 i + 63, B - 1) ascending
+ *     loss = (sum from +0 of seg[i], i ascending) * inv_count
+ * The segment length 64 is a constant: the order depends on B alone, never on the row tile or the grid.
+ *
+ * Backward.  A_l [B, H_l]: the output of hidden layer l behind its ReLU; A_{-1} = x, the features.  dZ_l:
+ * the gradient at layer l's pre-activation; the head's (l = n_layers) is dq.  O16 / B4: a count rounded
+ * up to 16 / 4, the padding terms +0 * +0 (they turn an accumulator of -0 into +0, nothing else).
+ *     dA_{l-1}[b][k] = chain over o = 0 .. O16_l - 1 ascending from +0: acc = fmaf(dZ_l[b][o], W_l[o][k], acc)
+ *     dZ_{l-1}[b][k] = A_{l-1}[b][k] > 0 ? dA_{l-1}[b][k] : +0        (a unit at +-0 passes nothing)
+ *     dW_l[o][k] = chain over b = 0 .. B4 - 1 ascending from +0: acc = fmaf(dZ_l[b][o], A_{l-1}[b][k], acc)
+ *     db_l[o]    = chain over b = 0 .. B4 - 1 ascending from +0: acc = fmaf(dZ_l[b][o], b < B ? 1.0f : +0, acc)
+ * One accumulator per output, no split of any sum, no atomics: v_mfma_f32_16x16x4_f32 meets each chain bit
+ * for bit (four terms per instruction, in ascending order).  A NaN in a row of target_quantiles makes the
+ * loss NaN and poisons every sum its dq reaches, as in torch; a NaN feature goes through the forward's
+ * relu(v) = v > 0 ? v : +0 as in pgx_qc_forward.
+ *
+ * Adam (torch.optim.Adam as SB3 builds it: no weight decay, no amsgrad), per parameter element with its
+ * gradient g, in f32, every operation rounded on its own:
+ *     step = step + 1                                              (a 64-bit device word)
+ *     p1 = beta1 ^ step, p2 = beta2 ^ step in double by squaring: p = 1, s = beta; for the bits of step
+ *          from the lowest: if the bit is set p = p * s; then s = s * s
+ *     bc1 = (float)(1.0 - p1); bc2 = (float)(1.0 - p2)
+ *     step_size = lr / bc1; c2 = sqrtf(bc2)                       (lr: one device float, read at every launch)
+ *     m = m + (g - m) * (float)(1.0 - beta1)
+ *     v = v * (float)beta2 + (float)(1.0 - beta2) * (g * g)
+ *     u = step_size * (m / (sqrtf(v) / c2 + (float)eps))
+ *     p = u == 0 ? p : p - u                                       (lr = 0 leaves every bit of p alone)
+ * then the online set is packed again, and so is the transposed packing the backward reads.
+ *
+ * Workspace.  The backward needs every row's activations and dZ; the handle keeps no batch-sized storage.
+ * The caller passes pgx_qc_grad_workspace_floats(cfg, B) floats: per row, K16 features, per critic the A_l
+ * and dZ_l planes (each width rounded up to 16), and 16 floats of loss terms.  Rows past B are never
+ * written.  The gradient buffer (torch layout, as pgx_qc_weights addresses it), exp_avg, exp_avg_sq, the
+ * step word and the transposed packing live in the handle, allocated by pgx_qc_init_training, never by a
+ * launch entry.  pgx_qc_critic_grad and pgx_qc_adam_step enqueue kernel launches only (no memcpy or
+ * memset node, no allocation, no sync).
+ * ---------------------------------------------------------------------- */
+typedef struct pgx_qc_grad_io {
+    const float* obs;              /* [B,obs_dim] */
+    const float* achieved_goal;    /* [B,3] */
+    const float* desired_goal;     /* [B,3] */
+    const float* action;           /* [B,action_dim] */
+    const float* target_quantiles; /* [B,n_target], dense (pgx_qc_target's out) */
+    float* workspace;              /* workspace_floats floats */
+    float* loss;                   /* one float */
+    float* quantiles_out;          /* debug [B,n_critics,n_quantiles] or NULL: q */
+    float* dq_out;                 /* debug [B,n_critics,n_quantiles] or NULL */
+    float* dz_out;                 /* debug [B, n_critics * (hidden[0] + .. )] or NULL: dZ_l of critic c at
+                                      column c * sum(hidden) + hidden[0] + .. + hidden[l - 1] */
+    int64_t workspace_floats;      /* >= pgx_qc_grad_workspace_floats(cfg, B) */
+    int32_t obs_stride;            /* >= obs_dim */
+    int32_t achieved_goal_stride;  /* >= 3 */
+    int32_t desired_goal_stride;   /* >= 3 */
+    int32_t action_stride;         /* >= action_dim */
+} pgx_qc_grad_io;
+
+/* Floats of workspace one pgx_qc_critic_grad of B rows needs; negative (PGX_E_INVALID) for a config
+ * pgx_qc_create refuses or B <= 0. */
+int64_t pgx_qc_grad_workspace_floats(const pgx_qc_config* cfg, int32_t B);
+/* Allocates the training state (see above), zeroes exp_avg, exp_avg_sq and step, and packs the online
+ * set's transposed copy.  Again: zeroes the state and takes the new constants, allocates nothing.
+ * PGX_E_INVALID naming the field for beta1 / beta2 outside [0, 1), eps not finite or <= 0. */
+int pgx_qc_init_training(pgx_qc_handle h, double beta1, double beta2, double eps);
+/* The loss and the gradient buffer of one batch: two launches.  pgx_qc_forward's refusals on obs ..
+ * action, and, naming the field: a NULL target_quantiles / workspace / loss, n_target outside 1..T,
+ * workspace_floats below pgx_qc_grad_workspace_floats; "pgx_qc_init_training" where that was not called.
+ * A refusal launches nothing. */
+int pgx_qc_critic_grad(pgx_qc_handle h, const pgx_qc_grad_io* io, int32_t B, int32_t n_target, void* stream);
+/* The gradient buffer into w's pointers (device or host), then a synchronise of `stream`. */
+int pgx_qc_get_grads(pgx_qc_handle h, const pgx_qc_weights* w, void* stream);
+/* One Adam step on the online set from the gradient buffer (see above).  lr: one device float. */
+int pgx_qc_adam_step(pgx_qc_handle h, const float* lr, void* stream);
+/* The optimiser state, for checkpoints: exp_avg / exp_avg_sq in torch layout, and the step word.  get
+ * synchronises `stream` behind its copies; set synchronises, then writes all three. */
+int pgx_qc_get_opt_state(pgx_qc_handle h, const pgx_qc_weights* exp_avg, const pgx_qc_weights* exp_avg_sq,
+                         uint64_t* step, void* stream);
+int pgx_qc_set_opt_state(pgx_qc_handle h, const pgx_qc_weights* exp_avg, const pgx_qc_weights* exp_avg_sq,
+                         uint64_t step, void* stream);
+/* The contracts above in plain C++ on host arrays (std::fmaf), with the device entries' refusals (one
+ * launch check serves both).  critic_grad_host: w the online set, grads written through its pointers,
+ * *io->loss, the debug planes where non-NULL, io->workspace used as the device entry uses it.
+ * adam_step_host: params, exp_avg and exp_avg_sq updated in place, *step moved on.  Never touch a device. */
+int pgx_qc_critic_grad_host(const pgx_qc_config* cfg, const pgx_qc_weights* w, const pgx_qc_grad_io* io, int32_t B,
+                            int32_t n_target, const pgx_qc_weights* grads);
+int pgx_qc_adam_step_host(const pgx_qc_config* cfg, const pgx_qc_weights* params, const pgx_qc_weights* grads,
+                          const pgx_qc_weights* exp_avg, const pgx_qc_weights* exp_avg_sq, uint64_t* step, double lr,
+                          double beta1, double beta2, double eps);
 
 #ifdef __cplusplus
 }

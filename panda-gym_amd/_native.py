@@ -147,6 +147,16 @@ SIGNATURES: Dict[str, Tuple[list, Any]] = {
     "pgx_qc_sync_target": _int(P, P),
     "pgx_qc_forward_host": _int(ptr(abi.PgxQcConfig), ptr(abi.PgxQcWeights), ptr(abi.PgxQcIo), I32),
     "pgx_qc_target_host": _int(ptr(abi.PgxQcConfig), ptr(abi.PgxQcWeights), ptr(abi.PgxQcIo), I32, I32),
+    "pgx_qc_grad_workspace_floats": ([ptr(abi.PgxQcConfig), I32], I64),
+    "pgx_qc_init_training": _int(P, C.c_double, C.c_double, C.c_double),
+    "pgx_qc_critic_grad": _int(P, ptr(abi.PgxQcGradIo), I32, I32, P),
+    "pgx_qc_get_grads": _int(P, ptr(abi.PgxQcWeights), P),
+    "pgx_qc_adam_step": _int(P, P, P),
+    "pgx_qc_get_opt_state": _int(P, ptr(abi.PgxQcWeights), ptr(abi.PgxQcWeights), ptr(U64), P),
+    "pgx_qc_set_opt_state": _int(P, ptr(abi.PgxQcWeights), ptr(abi.PgxQcWeights), U64, P),
+    "pgx_qc_critic_grad_host": _int(ptr(abi.PgxQcConfig), ptr(abi.PgxQcWeights), ptr(abi.PgxQcGradIo), I32, I32,
+                                    ptr(abi.PgxQcWeights)),
+    "pgx_qc_adam_step_host": _int(ptr(abi.PgxQcConfig), *[ptr(abi.PgxQcWeights)] * 4, ptr(U64), *[C.c_double] * 4),
 }
 
 # what load() requires of a library: a list the A/B tools filter before they load an older build

@@ -384,6 +384,17 @@ class PgxQcIo(C.Structure):
     ]
 
 
+class PgxQcGradIo(C.Structure):
+    _fields_ = [
+        ("obs", C.c_void_p), ("achieved_goal", C.c_void_p), ("desired_goal", C.c_void_p), ("action", C.c_void_p),
+        ("target_quantiles", C.c_void_p), ("workspace", C.c_void_p), ("loss", C.c_void_p),
+        ("quantiles_out", C.c_void_p), ("dq_out", C.c_void_p), ("dz_out", C.c_void_p),
+        ("workspace_floats", C.c_int64),
+        ("obs_stride", C.c_int32), ("achieved_goal_stride", C.c_int32), ("desired_goal_stride", C.c_int32),
+        ("action_stride", C.c_int32),
+    ]
+
+
 def rollout_row_fields(obs_dim: int, action_dim: int):
     """(name, offset, width) of the RolloutBuffer batch row layout of include/pgx.h, plus row_dim."""
     f, o = [], 0

@@ -16,7 +16,9 @@
  * action log-probability entries' contracts (the Actor's and the SdeActor's batch launches): the forward's
  * planes, the padded noise and variance chains of the gSDE distribution, and the unfused epilogues through
  * the host's libm; their launch checks, pgx_actor_lp_check_launch and pgx_sde_actor_lp_check_launch, are the
- * device entries' too.
+ * device entries' too.  pgx_qc_critic_grad_host and pgx_qc_adam_step_host (last) restate the critic update:
+ * the quantile Huber loss, the Linears' backward and Adam in the header's orders, behind
+ * pgx_qc_check_grad_launch and pgx_qc_check_adam, which the device entries call as well.
  */
 #include <algorithm>
 #include <cmath>
@@ -551,5 +553,233 @@ extern "C" int pgx_qc_target_host(const pgx_qc_config* cfg, const pgx_qc_weights
                 qc_backup(q[order[k]], ent, io->next_log_prob[b], io->reward[(size_t)b * io->reward_stride],
                           io->done[(size_t)b * io->done_stride], gamma);
     }
+    return PGX_OK;
+}
+
+/* ---------------------------------------------------------------- QuantileCritic, the critic update */
+
+/* floats of one workspace row: x [K16] | per critic A_0 .. A_{nl-1}, dZ_0 .. dZ_nl (widths up to 16) | 16 */
+int64_t pgx_qc_grad_row_floats(const pgx_qc_config* c) {
+    int64_t per_critic = (c->n_quantiles + 15) / 16 * 16;
+    for (int l = 0; l < c->n_layers; l++) per_critic += 2 * ((c->hidden[l] + 15) / 16 * 16);
+    return (c->obs_dim + 6 + c->action_dim + 15) / 16 * 16 + c->n_critics * per_critic + 16;
+}
+
+extern "C" int64_t pgx_qc_grad_workspace_floats(const pgx_qc_config* cfg, int32_t B) {
+    const char* what = "pgx_qc_grad_workspace_floats";
+    const int rc = pgx_qc_check_config(cfg, what);
+    if (rc != PGX_OK) return rc;
+    if (B <= 0) return bad(what, "B must be > 0");
+    return (int64_t)B * pgx_qc_grad_row_floats(cfg);
+}
+
+/* the checks of one pgx_qc_critic_grad launch, device and host alike */
+int pgx_qc_check_grad_launch(const pgx_qc_config* c, const pgx_qc_grad_io* io, int32_t B, int32_t n_target,
+                             const char* what) {
+    if (!io) return bad(what, "null io");
+    if (!io->obs) return bad(what, "null obs");
+    if (!io->achieved_goal) return bad(what, "null achieved_goal");
+    if (!io->desired_goal) return bad(what, "null desired_goal");
+    if (!io->action) return bad(what, "null action");
+    if (!io->target_quantiles) return bad(what, "null target_quantiles");
+    if (!io->workspace) return bad(what, "null workspace");
+    if (!io->loss) return bad(what, "null loss");
+    if (B <= 0) return bad(what, "B must be > 0");
+    if (io->obs_stride < c->obs_dim) return bad(what, "obs_stride is below obs_dim");
+    if (io->achieved_goal_stride < 3) return bad(what, "achieved_goal_stride is below 3");
+    if (io->desired_goal_stride < 3) return bad(what, "desired_goal_stride is below 3");
+    if (io->action_stride < c->action_dim) return bad(what, "action_stride is below action_dim");
+    if (n_target < 1 || n_target > c->n_critics * c->n_quantiles) return bad(what, "n_target must be in 1..n_critics * n_quantiles");
+    if (io->workspace_floats < (int64_t)B * pgx_qc_grad_row_floats(c))
+        return bad(what, "workspace_floats is below pgx_qc_grad_workspace_floats(cfg, B)");
+    return PGX_OK;
+}
+
+/* pgx_qc_init_training's and the host Adam's constants */
+int pgx_qc_check_adam(double beta1, double beta2, double eps, const char* what) {
+    if (!(beta1 >= 0.0 && beta1 < 1.0)) return bad(what, "beta1 must be in [0, 1)");
+    if (!(beta2 >= 0.0 && beta2 < 1.0)) return bad(what, "beta2 must be in [0, 1)");
+    if (!(eps > 0.0) || std::isinf(eps)) return bad(what, "eps must be finite and > 0");
+    return PGX_OK;
+}
+
+float pgx_qc_inv_count(const pgx_qc_config* c, int32_t B, int32_t n_target) {
+    return 1.0f / (float)((int64_t)B * c->n_critics * c->n_quantiles * n_target);
+}
+
+namespace {
+
+#pragma clang fp contract(off)
+/* one (row, critic, quantile) of the loss: the two chains over the row's targets */
+void qc_huber_chains(float q, const float* t, int nt, float tau, float* lt, float* gs) {
+    float a_l = 0.0f, a_g = 0.0f;
+    for (int k = 0; k < nt; k++) {
+        const float d = t[k] - q;
+        const float w = std::fabs(tau - (d < 0.0f ? 1.0f : 0.0f));
+        const float ad = std::fabs(d);
+        const float huber = ad > 1.0f ? ad - 0.5f : (d * d) * 0.5f;
+        const float clamp = d < -1.0f ? -1.0f : (d > 1.0f ? 1.0f : d);
+        a_l = std::fmaf(w, huber, a_l);
+        a_g = std::fmaf(w, clamp, a_g);
+    }
+    *lt = a_l;
+    *gs = a_g;
+}
+
+/* beta ^ step in double by squaring, the lowest bit first */
+double pow_by_squaring(double beta, uint64_t step) {
+    double p = 1.0, s = beta;
+    for (uint64_t n = step; n; n >>= 1) {
+        if (n & 1) p = p * s;
+        s = s * s;
+    }
+    return p;
+}
+
+void adam_element(float* p, float g, float* m, float* v, float step_size, float c2, float omb1, float b2, float omb2,
+                  float eps) {
+    *m = *m + (g - *m) * omb1;
+    *v = *v * b2 + omb2 * (g * g);
+    const float u = step_size * (*m / (std::sqrt(*v) / c2 + eps));
+    if (!(u == 0.0f)) *p = *p - u;
+}
+#pragma clang fp contract(on)
+
+int up16(int n) { return (n + 15) / 16 * 16; }
+
+}  // namespace
+
+extern "C" int pgx_qc_critic_grad_host(const pgx_qc_config* cfg, const pgx_qc_weights* w, const pgx_qc_grad_io* io,
+                                       int32_t B, int32_t n_target, const pgx_qc_weights* grads) {
+    const char* what = "pgx_qc_critic_grad_host";
+    int rc = pgx_qc_check_config(cfg, what);
+    if (rc == PGX_OK) rc = pgx_qc_check_weights(cfg, w, what);
+    if (rc == PGX_OK) rc = pgx_qc_check_grad_launch(cfg, io, B, n_target, what);
+    if (rc == PGX_OK) rc = pgx_qc_check_weights(cfg, grads, what);
+    if (rc != PGX_OK) return rc;
+    const int od = cfg->obs_dim, A = cfg->action_dim, nl = cfg->n_layers, nq = cfg->n_quantiles, nc = cfg->n_critics;
+    const int K = od + 6 + A, K16 = up16(K), Q16 = up16(nq), T = nc * nq;
+    int sumH = 0, sumH16 = 0;
+    for (int l = 0; l < nl; l++) {
+        sumH += cfg->hidden[l];
+        sumH16 += up16(cfg->hidden[l]);
+    }
+    const int64_t W = pgx_qc_grad_row_floats(cfg);
+    const int CW = 2 * sumH16 + Q16, loss_off = K16 + nc * CW;
+    /* workspace columns of critic c: A_l, dZ_l (l = nl: the head's) */
+    auto a_off = [&](int c, int l) {
+        int o = K16 + c * CW;
+        for (int i = 0; i < l; i++) o += up16(cfg->hidden[i]);
+        return o;
+    };
+    auto dz_off = [&](int c, int l) { return a_off(c, l) + sumH16; };
+    auto width = [&](int l) { return l < nl ? cfg->hidden[l] : nq; };
+    const float inv_count = pgx_qc_inv_count(cfg, B, n_target);
+    float* ws = io->workspace;
+    for (int32_t b = 0; b < B; b++) {
+        float* row = ws + (size_t)b * W;
+        for (int64_t i = 0; i < W; i++) row[i] = 0.0f;
+        for (int k = 0; k < 3; k++) row[k] = io->achieved_goal[(size_t)b * io->achieved_goal_stride + k];
+        for (int k = 0; k < 3; k++) row[3 + k] = io->desired_goal[(size_t)b * io->desired_goal_stride + k];
+        for (int k = 0; k < od; k++) row[6 + k] = io->obs[(size_t)b * io->obs_stride + k];
+        for (int k = 0; k < A; k++) row[6 + od + k] = io->action[(size_t)b * io->action_stride + k];
+        float q[PGX_QC_MAX_QUANTILES];
+        float rl = 0.0f;
+        for (int c = 0; c < nc; c++) {
+            const float* in = row;
+            int Kin = K;
+            for (int l = 0; l < nl; l++) {
+                linear(w->weight[c][l], w->bias[c][l], in, Kin, cfg->hidden[l], true, row + a_off(c, l));
+                in = row + a_off(c, l);
+                Kin = cfg->hidden[l];
+            }
+            linear(w->weight[c][nl], w->bias[c][nl], in, Kin, nq, false, q);
+            float* dq = row + dz_off(c, nl);
+            for (int j = 0; j < nq; j++) {
+                const float tau = ((float)j + 0.5f) / (float)nq;
+                float lt, gs;
+                qc_huber_chains(q[j], io->target_quantiles + (size_t)b * n_target, n_target, tau, &lt, &gs);
+                dq[j] = (-inv_count) * gs;
+                rl = rl + lt;
+                const size_t o = (size_t)b * T + c * nq + j;
+                if (io->quantiles_out) io->quantiles_out[o] = q[j];
+                if (io->dq_out) io->dq_out[o] = dq[j];
+            }
+            for (int l = nl; l >= 1; l--) {
+                const int out = width(l), O16 = up16(out), Kl = cfg->hidden[l - 1];
+                const float* dz = row + dz_off(c, l);
+                const float* act = row + a_off(c, l - 1);
+                float* dzp = row + dz_off(c, l - 1);
+                const float* Wl = w->weight[c][l];
+                for (int k = 0; k < Kl; k++) {
+                    float acc = 0.0f;
+                    for (int o = 0; o < out; o++) acc = std::fmaf(dz[o], Wl[(size_t)o * Kl + k], acc);
+                    for (int o = out; o < O16; o++) acc = std::fmaf(0.0f, 0.0f, acc);
+                    dzp[k] = act[k] > 0.0f ? acc : 0.0f;
+                    if (io->dz_out) {
+                        int col = c * sumH + k;
+                        for (int i = 0; i < l - 1; i++) col += cfg->hidden[i];
+                        io->dz_out[(size_t)b * nc * sumH + col] = dzp[k];
+                    }
+                }
+            }
+        }
+        row[loss_off] = rl;
+    }
+    const int B4 = (B + 3) / 4 * 4;
+    for (int c = 0; c < nc; c++)
+        for (int l = 0; l <= nl; l++) {
+            const int out = width(l), in = l == 0 ? K : cfg->hidden[l - 1];
+            const int ao = l == 0 ? 0 : a_off(c, l - 1), zo = dz_off(c, l);
+            float* dW = const_cast<float*>(grads->weight[c][l]);
+            float* db = const_cast<float*>(grads->bias[c][l]);
+            for (int o = 0; o < out; o++) {
+                for (int k = 0; k < in; k++) {
+                    float acc = 0.0f;
+                    for (int b = 0; b < B; b++) acc = std::fmaf(ws[(size_t)b * W + zo + o], ws[(size_t)b * W + ao + k], acc);
+                    for (int b = B; b < B4; b++) acc = std::fmaf(0.0f, 0.0f, acc);
+                    dW[(size_t)o * in + k] = acc;
+                }
+                float acc = 0.0f;
+                for (int b = 0; b < B; b++) acc = std::fmaf(ws[(size_t)b * W + zo + o], 1.0f, acc);
+                for (int b = B; b < B4; b++) acc = std::fmaf(0.0f, 0.0f, acc);
+                db[o] = acc;
+            }
+        }
+    float total = 0.0f;
+    for (int32_t b0 = 0; b0 < B; b0 += 64) {
+        float seg = 0.0f;
+        for (int32_t b = b0; b < B && b < b0 + 64; b++) seg = seg + ws[(size_t)b * W + loss_off];
+        total = total + seg;
+    }
+    *io->loss = total * inv_count;
+    return PGX_OK;
+}
+
+extern "C" int pgx_qc_adam_step_host(const pgx_qc_config* cfg, const pgx_qc_weights* params, const pgx_qc_weights* grads,
+                                     const pgx_qc_weights* exp_avg, const pgx_qc_weights* exp_avg_sq, uint64_t* step,
+                                     double lr, double beta1, double beta2, double eps) {
+    const char* what = "pgx_qc_adam_step_host";
+    int rc = pgx_qc_check_config(cfg, what);
+    if (rc == PGX_OK) rc = pgx_qc_check_adam(beta1, beta2, eps, what);
+    for (const pgx_qc_weights* w : {params, grads, exp_avg, exp_avg_sq})
+        if (rc == PGX_OK) rc = pgx_qc_check_weights(cfg, w, what);
+    if (rc != PGX_OK) return rc;
+    if (!step) return bad(what, "null step");
+    *step += 1;
+    const float bc1 = (float)(1.0 - pow_by_squaring(beta1, *step)), bc2 = (float)(1.0 - pow_by_squaring(beta2, *step));
+    const float step_size = (float)lr / bc1, c2 = std::sqrt(bc2);
+    const float omb1 = (float)(1.0 - beta1), b2 = (float)beta2, omb2 = (float)(1.0 - beta2), e = (float)eps;
+    const int nl = cfg->n_layers, K = cfg->obs_dim + 6 + cfg->action_dim;
+    for (int c = 0; c < cfg->n_critics; c++)
+        for (int l = 0; l <= nl; l++) {
+            const int out = l < nl ? cfg->hidden[l] : cfg->n_quantiles, in = l == 0 ? K : cfg->hidden[l - 1];
+            for (int pass = 0; pass < 2; pass++) {
+                auto at = [&](const pgx_qc_weights* w) { return const_cast<float*>(pass ? w->bias[c][l] : w->weight[c][l]); };
+                float *p = at(params), *g = at(grads), *m = at(exp_avg), *v = at(exp_avg_sq);
+                const size_t n = pass ? (size_t)out : (size_t)out * in;
+                for (size_t i = 0; i < n; i++) adam_element(p + i, g[i], m + i, v + i, step_size, c2, omb1, b2, omb2, e);
+            }
+        }
     return PGX_OK;
 }

@@ -16,7 +16,14 @@ are test oracles).
 ``next_actions`` and ``next_log_prob`` are the caller's buffers: ``Actor.action_log_prob_rows`` /
 ``SdeActor.action_log_prob_rows`` fill them from the same batch in one launch (actor.py, sde_actor.py).
 
-Not here: gradients, the quantile Huber loss, the actor loss's Q mean, optimisers.
+The critic update runs there too (include/pgx.h, "QuantileCritic, the critic update"): ``critic_loss_backward``
+is ``quantile_huber_loss(critic(obs, actions), target_quantiles)`` and its gradient for every online parameter
+in two launches, ``adam_step`` is ``torch.optim.Adam``'s step on them with the learning rate read from the
+device, and both capture behind ``td_target_rows`` in one graph.  ``critic_grad_host`` / ``adam_step_host`` are
+the host models of that arithmetic (test oracles).
+
+Not here: the actor loss's Q mean and dQ/d(action), the ``ent_coef`` loss, the actor's optimiser, gradient
+clipping.
 """
 from __future__ import annotations
 
@@ -26,7 +33,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import abi
-from ._native import check
+from ._native import PgxError, check
 from ._policy import Policy, torch
 
 SETS = ("online", "target")
@@ -74,7 +81,12 @@ class QuantileCritic(Policy):
         self._bs = {s: [z(shp[0]) for _ in range(nc) for shp in shapes] for s in SETS}
         self._n_linear = len(shapes)
         self._loading: Tuple[str, ...] = SETS
-        self._stale = False   # the target tensors here lag the handle's copy (after a Polyak step or a sync)
+        # The tensors here may lag the handle's copies: the target's once a Polyak step or a sync was enqueued,
+        # the online set's once an Adam step was.  They stay set: a captured graph moves the handle's copies at
+        # every replay, and nothing here sees a replay.
+        self._stale = False
+        self._stale_online = False
+        self._opt: Optional[Tuple[float, float, float]] = None   # (beta1, beta2, eps) once init_optimizer ran
         self._open()
 
     # ------------------------------------------------------------ plumbing
@@ -110,11 +122,14 @@ class QuantileCritic(Policy):
             self._call("set_weights", self._h, abi.QC_SETS[s], C.byref(w), self._stream())
 
     def _pull_target(self) -> None:
-        """The handle's plain copy of the target set into the tensors here (after a Polyak step or a sync)."""
+        """The handle's plain copies into the tensors here: the target set after a Polyak step or a sync, the
+        online set after an Adam step."""
         if self._h is not None and self._stale:
             w = self._set_struct("target")
             self._call("get_weights", self._h, abi.QC_TARGET, C.byref(w), self._stream())
-            self._stale = False
+        if self._h is not None and self._stale_online:
+            w = self._set_struct("online")
+            self._call("get_weights", self._h, abi.QC_ONLINE, C.byref(w), self._stream())
 
     # ----------------------------------------------------------- parameters
     def _set_pairs(self, which: str, prefix: str = "") -> List[Tuple[str, "torch.Tensor"]]:
@@ -152,13 +167,11 @@ class QuantileCritic(Policy):
             sets = ("online",)
         if not prefixed:
             sd = {f"{SD_PREFIX[s]}{k}": v for s in sets for k, v in sd.items()}
-        if "target" not in sets:
-            self._pull_target()   # (a later state_dict must not read a stale target over this load)
+        if sets != SETS:
+            self._pull_target()   # (a later state_dict must not read a stale set over this load)
         self._loading = sets
         try:
             self._load_slots(sd)
-            if "target" in sets:
-                self._stale = False
         finally:
             self._loading = SETS
 
@@ -262,8 +275,7 @@ class QuantileCritic(Policy):
         return io, n, [o, a]
 
     def _host_set(self, which: str):
-        if which == "target":
-            self._pull_target()
+        self._pull_target()
         ws = [np.ascontiguousarray(t.cpu().numpy()) for t in self._ws[which]]
         bs = [np.ascontiguousarray(t.cpu().numpy()) for t in self._bs[which]]
         return self._weights_struct([x.ctypes.data for x in ws], [x.ctypes.data for x in bs]), [ws, bs]
@@ -297,3 +309,215 @@ class QuantileCritic(Policy):
         io.out, io.quantiles_out = abi.ptr(out), abi.ptr(pool)
         self._call("target_host", C.byref(self._cfg), C.byref(w), C.byref(io), n, nt)
         return (out, pool) if return_quantiles else out
+
+    # ------------------------------------------------------------ the critic update
+    def _like_online(self, device=None) -> Tuple[List["torch.Tensor"], List["torch.Tensor"]]:
+        dev = self.device if device is None else device
+        return ([torch.zeros_like(t, device=dev) for t in self._ws["online"]],
+                [torch.zeros_like(t, device=dev) for t in self._bs["online"]])
+
+    def _named(self, ws, bs) -> Dict[str, Any]:
+        out = {}
+        for name, w, b in zip(self._names, ws, bs):
+            out[f"{name}.weight"], out[f"{name}.bias"] = w, b
+        return out
+
+    def _unnamed(self, d: Dict[str, Any], what: str):
+        """``d`` (SB3 key names) as numpy weight and bias lists in ``_names`` order, every shape checked."""
+        ws, bs = [], []
+        for name, w, b in zip(self._names, self._ws["online"], self._bs["online"]):
+            for key, cur, dst in ((f"{name}.weight", w, ws), (f"{name}.bias", b, bs)):
+                if key not in d:
+                    raise KeyError(f"{what}: missing key {key!r}")
+                v = d[key]
+                x = np.array(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float32, order="C")
+                if x.shape != tuple(cur.shape):
+                    raise ValueError(f"{what}: {key!r} has shape {x.shape}, expected {tuple(cur.shape)}")
+                dst.append(x)
+        return ws, bs
+
+    def init_optimizer(self, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8) -> None:
+        """``torch.optim.Adam(critic.parameters(), betas=, eps=)`` as SB3 builds it (no weight decay, no
+        amsgrad): allocates the handle's gradient buffer, ``exp_avg``, ``exp_avg_sq``, the step word and the
+        packing the backward reads; called again, zeroes the state.  Not a launch: call it before a capture."""
+        b1, b2, e = float(betas[0]), float(betas[1]), float(eps)
+        if self._h is not None:
+            self._call("init_training", self._h, C.c_double(b1), C.c_double(b2), C.c_double(e))
+        else:
+            self.adam_step_host(0.0, self._named(*self._like_online()), betas=(b1, b2), eps=e)   # the library's checks
+            zeros = lambda: self._named(*[[t.numpy() for t in x] for x in self._like_online()])  # noqa: E731
+            self._cpu_state = {"exp_avg": zeros(), "exp_avg_sq": zeros(), "step": 0}
+        self._opt = (b1, b2, e)
+
+    def workspace_floats(self, batch: int) -> int:
+        n = int(self.lib.pgx_qc_grad_workspace_floats(C.byref(self._cfg), int(batch)))
+        if n < 0:
+            check(n, "pgx_qc_grad_workspace_floats", self.lib)
+        return n
+
+    def alloc_workspace(self, max_batch: int) -> "torch.Tensor":
+        """The workspace ``critic_loss_backward`` of up to ``max_batch`` rows needs (every row's activations
+        and pre-activation gradients: the handle keeps no batch-sized storage), an f32 device tensor; and
+        ``init_optimizer()`` with its defaults where that was not called."""
+        self._need_device()
+        if self._opt is None:
+            self.init_optimizer()
+        return torch.empty(self.workspace_floats(max_batch), dtype=torch.float32, device=self.device)
+
+    def alloc_grad_debug(self, batch: int) -> Dict[str, "torch.Tensor"]:
+        """Debug planes for ``critic_loss_backward(..., debug=)`` of ``batch`` rows: ``quantiles`` and ``dq``
+        [B, n_critics * n_quantiles], ``dz`` [B, n_critics * sum(net_arch)] (critic-major, then layer)."""
+        z = lambda w: torch.zeros((int(batch), w), dtype=torch.float32, device=self.device)  # noqa: E731
+        return {"quantiles": z(self.n_pool), "dq": z(self.n_pool), "dz": z(self.n_critics * sum(self.net_arch))}
+
+    def critic_loss_backward(self, obs: Dict[str, Any], actions, target_quantiles, workspace, loss=None,
+                             debug: Optional[Dict[str, "torch.Tensor"]] = None) -> "torch.Tensor":
+        """``critic_loss = quantile_huber_loss(critic(obs, actions), target_quantiles,
+        sum_over_quantiles=False)`` and ``critic_loss.backward()`` into the handle's gradient buffer (replaced,
+        never accumulated: ``zero_grad`` is implied): two launches.  ``target_quantiles``: a contiguous f32
+        device tensor [B, n_target] (``td_target``'s result; any ``n_target`` in 1..n_critics * n_quantiles).
+        ``workspace``: ``alloc_workspace``'s tensor.  Returns the loss, a device scalar (``loss``: a
+        one-float f32 device tensor to fill instead of a new one)."""
+        self._need_device()
+        io = abi.PgxQcGradIo()
+        qio, B, keep = self._io(obs, actions)
+        for f in ("obs", "achieved_goal", "desired_goal", "action"):
+            setattr(io, f, getattr(qio, f))
+            setattr(io, f + "_stride", getattr(qio, f + "_stride"))
+        tq = target_quantiles
+        if not torch.is_tensor(tq) or tq.dtype != torch.float32 or tq.device != self.device or tq.dim() != 2 \
+                or tq.shape[0] < B or not tq.is_contiguous():
+            raise ValueError(f"target_quantiles must be a contiguous f32 [>= {B}, n_target] tensor on {self.device}")
+        ws = workspace
+        if not torch.is_tensor(ws) or ws.dtype != torch.float32 or ws.device != self.device or not ws.is_contiguous():
+            raise ValueError(f"workspace must be a contiguous f32 tensor on {self.device} (alloc_workspace)")
+        if loss is None:
+            loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        elif not torch.is_tensor(loss) or loss.dtype != torch.float32 or loss.device != self.device or loss.numel() != 1:
+            raise ValueError(f"loss must be a one-float f32 tensor on {self.device}")
+        io.target_quantiles, io.workspace, io.loss = tq.data_ptr(), ws.data_ptr(), loss.data_ptr()
+        io.workspace_floats = ws.numel()
+        if debug is not None:
+            for k in ("quantiles", "dq", "dz"):
+                if debug[k].shape[0] < B or not debug[k].is_contiguous():
+                    raise ValueError(f"the debug planes hold {debug[k].shape[0]} rows, the batch {B}")
+                setattr(io, f"{k}_out", debug[k].data_ptr())
+        check(self.lib.pgx_qc_critic_grad(self._h, C.byref(io), B, int(tq.shape[1]), self._stream()),
+              "pgx_qc_critic_grad", self.lib)
+        self._keep = keep + [tq, ws, loss, debug]
+        return loss.view(())
+
+    def critic_loss_backward_rows(self, batch: Dict[str, "torch.Tensor"], target_quantiles, workspace, loss=None,
+                                  debug=None) -> "torch.Tensor":
+        """``critic_loss_backward`` on a HER batch (``buf.alloc_batch`` / ``buf.sample_into``): ``obs``,
+        ``achieved_goal``, ``desired_goal`` and ``action`` are read from ``batch["rows"]`` in place."""
+        return self.critic_loss_backward(self._batch_obs(batch, False), batch["action"], target_quantiles, workspace,
+                                         loss=loss, debug=debug)
+
+    def grads(self) -> Dict[str, "torch.Tensor"]:
+        """The gradient buffer as the last ``critic_loss_backward`` left it, under sb3_contrib's key names
+        ``qf{i}.{0,2,4}.weight|bias`` (copies)."""
+        self._need_device()
+        ws, bs = self._like_online()
+        w = self._weights_struct([t.data_ptr() for t in ws], [t.data_ptr() for t in bs])
+        self._call("get_grads", self._h, C.byref(w), self._stream())
+        return self._named(ws, bs)
+
+    def adam_step(self, lr) -> None:
+        """``critic.optimizer.step()``: one Adam step on the online set from the gradient buffer, then its
+        packing, on the current stream.  ``lr``: a one-float f32 device tensor, read at every launch (a
+        replayed graph sees its current value: a schedule writes it), or a number."""
+        self._need_device()
+        t = lr if torch.is_tensor(lr) else torch.as_tensor(float(lr))
+        if t.numel() != 1:
+            raise ValueError("lr must hold one float")
+        t = t.detach().to(device=self.device, dtype=torch.float32).reshape(1)
+        self._call("adam_step", self._h, t.data_ptr(), self._stream())
+        self._keep_lr = t
+        self._stale_online = True
+
+    def optimizer_state_dict(self) -> Dict[str, Any]:
+        """``exp_avg`` and ``exp_avg_sq`` (each under the parameters' key names, copies), ``step``, ``betas``
+        and ``eps``.  On a CPU device: the state this object holds (``load_optimizer_state_dict``'s)."""
+        if self._opt is None:
+            raise PgxError("no optimiser state: call init_optimizer first")
+        if self._h is None:
+            st = self._cpu_state
+            return {"exp_avg": {k: torch.as_tensor(x.copy()) for k, x in st["exp_avg"].items()},
+                    "exp_avg_sq": {k: torch.as_tensor(x.copy()) for k, x in st["exp_avg_sq"].items()},
+                    "step": st["step"], "betas": self._opt[:2], "eps": self._opt[2]}
+        m, v = self._like_online(), self._like_online()
+        sm = self._weights_struct([t.data_ptr() for t in m[0]], [t.data_ptr() for t in m[1]])
+        sv = self._weights_struct([t.data_ptr() for t in v[0]], [t.data_ptr() for t in v[1]])
+        step = C.c_uint64(0)
+        self._call("get_opt_state", self._h, C.byref(sm), C.byref(sv), C.byref(step), self._stream())
+        return {"exp_avg": self._named(*m), "exp_avg_sq": self._named(*v), "step": int(step.value),
+                "betas": self._opt[:2], "eps": self._opt[2]}
+
+    def load_optimizer_state_dict(self, sd: Dict[str, Any]) -> None:
+        """What ``optimizer_state_dict`` returned (``betas`` / ``eps`` are not read: ``init_optimizer`` sets
+        them).  Every key and shape is validated before anything is written: a failed load changes nothing."""
+        if self._opt is None:
+            raise PgxError("no optimiser state: call init_optimizer first")
+        step = int(sd["step"])
+        if step < 0:
+            raise ValueError("step must be >= 0")
+        m = self._unnamed(sd["exp_avg"], "load_optimizer_state_dict: exp_avg")
+        v = self._unnamed(sd["exp_avg_sq"], "load_optimizer_state_dict: exp_avg_sq")
+        if self._h is None:
+            self._cpu_state = {"exp_avg": self._named(*m), "exp_avg_sq": self._named(*v), "step": step}
+            return
+        sm = self._weights_struct([x.ctypes.data for x in m[0]], [x.ctypes.data for x in m[1]])
+        sv = self._weights_struct([x.ctypes.data for x in v[0]], [x.ctypes.data for x in v[1]])
+        self._call("set_opt_state", self._h, C.byref(sm), C.byref(sv), C.c_uint64(step), self._stream())
+        torch.cuda.synchronize(self.device)   # (the copies read the numpy arrays above)
+
+    def critic_grad_host(self, obs: Dict[str, Any], actions, target_quantiles, return_debug: bool = False):
+        """``(loss, grads)`` -- a numpy f32 scalar and numpy arrays under the parameters' key names -- from the
+        library's host model of ``critic_loss_backward`` on the online set; ``return_debug``: also the
+        ``quantiles`` / ``dq`` / ``dz`` planes.  A test oracle."""
+        qio, n, keep = self._host_io(obs, actions)
+        io = abi.PgxQcGradIo()
+        for f in ("obs", "achieved_goal", "desired_goal", "action"):
+            setattr(io, f, getattr(qio, f))
+            setattr(io, f + "_stride", getattr(qio, f + "_stride"))
+        tq = np.ascontiguousarray(target_quantiles.detach().cpu().numpy() if torch.is_tensor(target_quantiles)
+                                  else target_quantiles, dtype=np.float32)
+        if tq.ndim != 2 or tq.shape[0] != n:
+            raise ValueError(f"target_quantiles must be [{n}, n_target]")
+        w, keep_w = self._host_set("online")
+        ws = np.zeros(max(self.workspace_floats(n), 1), np.float32)
+        loss = np.zeros(1, np.float32)
+        dbg = {"quantiles": np.zeros((n, self.n_pool), np.float32), "dq": np.zeros((n, self.n_pool), np.float32),
+               "dz": np.zeros((n, self.n_critics * sum(self.net_arch)), np.float32)}
+        io.target_quantiles, io.workspace, io.loss, io.workspace_floats = abi.ptr(tq), abi.ptr(ws), abi.ptr(loss), ws.size
+        io.quantiles_out, io.dq_out, io.dz_out = abi.ptr(dbg["quantiles"]), abi.ptr(dbg["dq"]), abi.ptr(dbg["dz"])
+        gw = [np.zeros(tuple(t.shape), np.float32) for t in self._ws["online"]]
+        gb = [np.zeros(tuple(t.shape), np.float32) for t in self._bs["online"]]
+        g = self._weights_struct([x.ctypes.data for x in gw], [x.ctypes.data for x in gb])
+        self._call("critic_grad_host", C.byref(self._cfg), C.byref(w), C.byref(io), n, int(tq.shape[1]), C.byref(g))
+        out = (loss[0], self._named(gw, gb))
+        return out + (dbg,) if return_debug else out
+
+    def adam_step_host(self, lr: float, grads: Dict[str, Any], params: Optional[Dict[str, Any]] = None,
+                       state: Optional[Dict[str, Any]] = None, betas: Optional[Tuple[float, float]] = None,
+                       eps: Optional[float] = None):
+        """One Adam step by the library's host model, on copies: ``(params, state)`` after the step, from
+        ``params`` (default: the online set) and ``state`` (``exp_avg`` / ``exp_avg_sq`` / ``step`` as
+        ``optimizer_state_dict`` names them; default: zeros, step 0).  Nothing of this object changes.  A
+        test oracle."""
+        b1, b2, e = self._opt or (0.9, 0.999, 1e-8)
+        if betas is not None:
+            b1, b2 = float(betas[0]), float(betas[1])
+        if eps is not None:
+            e = float(eps)
+        p = self._unnamed(self.state_dict("online") if params is None else params, "adam_step_host: params")
+        g = self._unnamed(grads, "adam_step_host: grads")
+        zeros = self._named(*self._like_online("cpu"))
+        m = self._unnamed(zeros if state is None else state["exp_avg"], "adam_step_host: exp_avg")
+        v = self._unnamed(zeros if state is None else state["exp_avg_sq"], "adam_step_host: exp_avg_sq")
+        step = C.c_uint64(0 if state is None else int(state["step"]))
+        structs = [self._weights_struct([x.ctypes.data for x in a[0]], [x.ctypes.data for x in a[1]]) for a in (p, g, m, v)]
+        self._call("adam_step_host", C.byref(self._cfg), *[C.byref(x) for x in structs], C.byref(step), C.c_double(float(lr)),
+                   C.c_double(b1), C.c_double(b2), C.c_double(e))
+        return self._named(*p), {"exp_avg": self._named(*m), "exp_avg_sq": self._named(*v), "step": int(step.value)}
