@@ -1,6 +1,7 @@
 """What the device-resident policies (``Actor``, ``ActorCritic``, ``SdeActor``, ``QuantileCritic``) share on the
 Python side:
-resolving env, dims and device, the handle's life, the observation shaping in front of a launch, the
+resolving env, dims and device, the handle's life, the observation shaping in front of a launch (per env, or
+``_rows_into`` / ``_f32_out`` for the batch launches), the
 parameter slots behind ``state_dict`` / ``load_state_dict``, the numpy conversions in front of the host
 model, the device noise word, and the check of a venv's persistent buffers in front of a capture.
 """
@@ -135,28 +136,46 @@ class Policy(Handle):
         """Name -> width of the debug planes of ``action_log_prob``."""
         raise PgxError(f"{type(self).__name__} has no action_log_prob")
 
-    def _lp_io(self, io, obs: Dict[str, Any], out):
-        """Fills a batch launch's ``io`` (``PgxActorLpIo`` / ``PgxSdeActorLpIo``): the observation fields with
-        their row strides, read in place where they can be, and the outputs ``(actions [B, A], log_prob
-        [B])``, ``out`` or new tensors.  Returns (B, actions, log_prob, what the launch reads)."""
+    # ------------------------------------------------- batch launches (rows of any number, through row strides)
+    def _rows_into(self, io, obs: Dict[str, Any], actions=None):
+        """Fills any batch launch's ``io`` with the observation fields (and, given ``actions``, the action) and
+        their row strides, read in place where they can be.  Returns (B, what the launch reads)."""
         o, io.obs_stride = self._field(obs["observation"], self.obs_dim, None, "observation")
         B = int(o.shape[0])
         ag, io.achieved_goal_stride = self._field(obs["achieved_goal"], 3, B, "achieved_goal")
         dg, io.desired_goal_stride = self._field(obs["desired_goal"], 3, B, "desired_goal")
-        if out is None:
-            act = torch.empty((B, self.action_dim), dtype=torch.float32, device=self.device)
-            lp = torch.empty((B,), dtype=torch.float32, device=self.device)
-        else:
-            act, lp = out
-            for t, tail in ((act, (self.action_dim,)), (lp, ())):
-                if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != self.device \
-                        or not t.is_contiguous() or t.dim() != 1 + len(tail) or t.shape[0] < B \
-                        or tuple(t.shape[1:]) != tail:
-                    raise ValueError(f"out must be contiguous f32 tensors [>= {B}, {self.action_dim}] and [>= {B}] "
-                                     f"on {self.device} (rows past {B} are left alone)")
         io.obs, io.achieved_goal, io.desired_goal = o.data_ptr(), ag.data_ptr(), dg.data_ptr()
+        keep = [o, ag, dg]
+        if actions is not None:
+            a, io.action_stride = self._field(actions, self.action_dim, B, "actions")
+            io.action = a.data_ptr()
+            keep.append(a)
+        return B, keep
+
+    def _f32_out(self, t, B: int, tail: Tuple[Optional[int], ...], what: str) -> "torch.Tensor":
+        """``t`` where it is a contiguous f32 [>= B, *tail] tensor on this device (``None`` in ``tail``: any
+        width), for ``None`` a new one; anything else is refused with ``what``."""
+        if t is None:
+            return torch.empty((B,) + tuple(tail), dtype=torch.float32, device=self.device)
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() \
+                or t.dim() != 1 + len(tail) or t.shape[0] < B \
+                or any(w is not None and n != w for n, w in zip(t.shape[1:], tail)):
+            raise ValueError(what)
+        return t
+
+    def _lp_io(self, io, obs: Dict[str, Any], out):
+        """Fills an ``action_log_prob`` launch's ``io`` (``PgxActorLpIo`` / ``PgxSdeActorLpIo``): the observation
+        fields, and the outputs ``(actions [B, A], log_prob [B])``, ``out`` or new tensors.  Returns (B, actions,
+        log_prob, what the launch reads)."""
+        B, keep = self._rows_into(io, obs)
+        what = f"out must be contiguous f32 tensors [>= {B}, {self.action_dim}] and [>= {B}] on {self.device} " \
+               f"(rows past {B} are left alone)"
+        act, lp = (None, None) if out is None else out
+        if out is not None and (act is None or lp is None):
+            raise ValueError(what)
+        act, lp = self._f32_out(act, B, (self.action_dim,), what), self._f32_out(lp, B, (), what)
         io.action, io.log_prob = act.data_ptr(), lp.data_ptr()
-        return B, act, lp, [o, ag, dg]
+        return B, act, lp, keep
 
     def enable_log_prob_debug(self, B: int) -> Dict[str, "torch.Tensor"]:
         """Allocate the debug planes every later ``action_log_prob`` of ``B`` rows fills: f32 [B, width] per
@@ -189,13 +208,24 @@ class Policy(Handle):
         return {"observation": batch[p + "obs"], "achieved_goal": batch[p + "achieved_goal"],
                 "desired_goal": batch[p + "desired_goal"]}
 
-    def _host_lp_io(self, io, obs: Dict[str, Any], planes: Dict[str, int]):
-        """Fills ``io`` for a host model: dense numpy inputs, and every output and plane as a new array.
-        Returns (n, {name: array})."""
+    def _host_rows_into(self, io, obs: Dict[str, Any], actions=None):
+        """``_rows_into`` for a host model: dense numpy inputs.  Returns (n, what the call reads)."""
         o, n = self._host_obs(obs)
         io.obs, io.achieved_goal, io.desired_goal = (abi_ptr(o["observation"]), abi_ptr(o["achieved_goal"]),
                                                      abi_ptr(o["desired_goal"]))
         io.obs_stride, io.achieved_goal_stride, io.desired_goal_stride = self.obs_dim, 3, 3
+        if actions is None:
+            return n, [o]
+        a = np.ascontiguousarray(actions.cpu().numpy() if torch.is_tensor(actions) else actions, dtype=np.float32)
+        if o["observation"].shape != (n, self.obs_dim) or a.shape != (n, self.action_dim):
+            raise ValueError(f"expected observation [n, {self.obs_dim}] and actions [n, {self.action_dim}]")
+        io.action, io.action_stride = abi_ptr(a), self.action_dim
+        return n, [o, a]
+
+    def _host_lp_io(self, io, obs: Dict[str, Any], planes: Dict[str, int]):
+        """Fills ``io`` for a host model: dense numpy inputs, and every output and plane as a new array.
+        Returns (n, {name: array})."""
+        n, (o,) = self._host_rows_into(io, obs)
         res = {"action": np.zeros((n, self.action_dim), np.float32), "log_prob": np.zeros((n,), np.float32)}
         io.action, io.log_prob = abi_ptr(res["action"]), abi_ptr(res["log_prob"])
         for k, w in planes.items():

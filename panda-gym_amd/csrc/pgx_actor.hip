@@ -24,7 +24,7 @@
  * Log-probability kernel (pgx_actor_action_log_prob, SB3's actor.action_log_prob): the same workgroup
  * over a tile of 32 batch rows (16 for a batch of up to 16, or where 32 do not fit the LDS), the batch
  * size a launch argument and every observation field read through its own row stride (pgx_mlp.h's
- * stage_features_rows).  Behind the head tile the thread of (row, dimension) computes the squashed action
+ * stage_rows).  Behind the head tile the thread of (row, dimension) computes the squashed action
  * and its two log-probability terms with contraction off; the terms go through the dead activations
  * and the thread of dimension 0 adds them in ascending order.  Its noise word is another than the
  * forward's.
@@ -118,8 +118,8 @@ __global__ __launch_bounds__(THREADS) void actor_lp_kernel(ActorArgs a, pgx_acto
     const int row0 = blockIdx.x * ROWS;
     const bool draw = io.eps == nullptr;
     load_word(&sh_step, a.step, draw, tid);
-    stage_features_rows<MT>(lds, io.obs, io.achieved_goal, io.desired_goal, io.obs_stride, io.achieved_goal_stride,
-                            io.desired_goal_stride, row0, B, a.od, a.plan.nkb[0] * 16, S, tid);
+    stage_rows<MT>(lds, io.obs, io.achieved_goal, io.desired_goal, nullptr, io.obs_stride, io.achieved_goal_stride,
+                   io.desired_goal_stride, 0, row0, B, a.od, 0, a.plan.nkb[0] * 16, S, tid);
     __syncthreads();
     const int in_off = run_linears<MT>(lds, a.params, a.plan, a.plan.n_linear, false, 0, S, ROWS * S, 0, S, lane, wave);
     /* one thread per (row, dimension); the head tile lies at lds[in_off] */
@@ -220,18 +220,10 @@ int pgx_actor_create(const pgx_actor_config* cfg, int device, pgx_actor_handle* 
     a.ticket = (uint32_t*)((char*)ptr[2] + 8);
     h->lp_step = (unsigned long long*)((char*)ptr[2] + 16);
     h->lp_ticket = (uint32_t*)((char*)ptr[2] + 24);
-    if (cfg->kind == PGX_ACTOR_GAUSSIAN) {   /* the batch kernels' dynamic LDS: 16 rows always fit, 32 where they do */
-        const int mt_max = choose_tile(17, nullptr, [h](int mt) { return h->lds_need(mt); }, 17);
-        bool ok = hipFuncSetAttribute((const void*)actor_lp_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)h->lds_need(1)) == hipSuccess;
-        if (mt_max == 2)
-            ok = ok && hipFuncSetAttribute((const void*)actor_lp_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)h->lds_need(2)) == hipSuccess;
-        if (!ok) {
-            (void)hipFree(h->params);
-            delete h;
-            return pgx_set_error(PGX_E_HIP, "pgx_actor_create: device setup failed");
-        }
+    if (cfg->kind == PGX_ACTOR_GAUSSIAN && !set_tile_lds(actor_lp_kernel<1>, actor_lp_kernel<2>, lds_need)) {
+        (void)hipFree(h->params);
+        delete h;
+        return pgx_set_error(PGX_E_HIP, "pgx_actor_create: device setup failed");
     }
     *out = h;
     return PGX_OK;

@@ -8,8 +8,11 @@
  * bit, so the kernel is tested against this on the device and this against an independent
  * restatement on a CPU.  Never touches a device; the Actor does not step through it.
  * pgx_ac_forward_host and pgx_sde_actor_forward_host (below) are the same for pgx_actor_critic.hip and
- * pgx_sde_actor.hip, over the same `stage_x`, `hidden_layers` and `linear`; the three check_config share
- * `check_common`, `check_count` and `check_widths`.  pgx_qc_forward_host and pgx_qc_target_host (last) are
+ * pgx_sde_actor.hip, over the same `stage_row`, `hidden_layers` and `linear`; the check_config share
+ * `check_dims`, `check_common`, `check_count` and `check_widths`.  `stage_row` is every model's stager: it reads each
+ * field through a row stride, (obs_dim, 3, 3) for the dense per-env models, with the action columns for the quantile
+ * critics.  The three batch launch checks share `check_rows_ptrs` and `check_rows_shape`, each launch's own pointers
+ * checked between the two, so the message that wins for any set of bad fields is the one that always did.  pgx_qc_forward_host and pgx_qc_target_host (last) are
  * the quantile critics' (pgx_quantile_critic.hip): the same Linears, then the pooled sort by the order
  * rule's key, the truncation and the unfused Bellman backup; the launch checks they share with the device
  * entry points are pgx_qc_check_launch.  pgx_actor_log_prob_host and pgx_sde_actor_log_prob_host are the
@@ -39,14 +42,19 @@ int bad(const char* what, const char* field, const char* rest = "") {
     return pgx_set_error(PGX_E_INVALID, msg);
 }
 
-/* what the three configs share */
+/* what the four configs share, ... */
+int check_dims(const char* what, int obs_dim, int action_dim) {
+    if (obs_dim <= 0 || obs_dim > 4096) return bad(what, "obs_dim must be in 1..4096");
+    if (action_dim < 1 || action_dim > PGX_ACTOR_MAX_ACTION) return bad(what, "action_dim must be in 1..7");
+    return PGX_OK;
+}
+
+/* ... and the three that hold per-env state */
 template <class Config>
 int check_common(const Config* c, const char* what, bool with_envs) {
     if (!c) return bad(what, "null config");
     if (with_envs && c->n_envs <= 0) return bad(what, "n_envs must be > 0");
-    if (c->obs_dim <= 0 || c->obs_dim > 4096) return bad(what, "obs_dim must be in 1..4096");
-    if (c->action_dim < 1 || c->action_dim > PGX_ACTOR_MAX_ACTION) return bad(what, "action_dim must be in 1..7");
-    return PGX_OK;
+    return check_dims(what, c->obs_dim, c->action_dim);
 }
 
 /* a stack's layer count, then its widths; `name` is the config field's */
@@ -62,6 +70,36 @@ int check_widths(const char* what, const char* name, int n, const int32_t* width
 
 int check_clip_mean(const char* what, double clip_mean) {
     return !(clip_mean >= 0.0) || std::isinf(clip_mean) ? bad(what, "clip_mean must be finite and >= 0") : PGX_OK;
+}
+
+int up16(int n) { return (n + 15) / 16 * 16; }
+
+float clip_to(float m, float clip) { return clip > 0.0f ? (m < -clip ? -clip : (m > clip ? clip : m)) : m; }
+
+float clamp_log_std(float v) {
+    return v < PGX_ACTOR_LOG_STD_MIN ? PGX_ACTOR_LOG_STD_MIN : (v > PGX_ACTOR_LOG_STD_MAX ? PGX_ACTOR_LOG_STD_MAX : v);
+}
+
+/* What the three batch launches' checks share, each launch's own pointers checked in between: io and the
+ * pointers every one of them reads ... */
+template <class Io>
+int check_rows_ptrs(const Io* io, const char* what) {
+    if (!io) return bad(what, "null io");
+    if (!io->obs) return bad(what, "null obs");
+    if (!io->achieved_goal) return bad(what, "null achieved_goal");
+    if (!io->desired_goal) return bad(what, "null desired_goal");
+    if (!io->action) return bad(what, "null action");
+    return PGX_OK;
+}
+
+/* ... and B and the observation fields' row strides */
+template <class Io>
+int check_rows_shape(const Io* io, int32_t B, int obs_dim, const char* what) {
+    if (B <= 0) return bad(what, "B must be > 0");
+    if (io->obs_stride < obs_dim) return bad(what, "obs_stride is below obs_dim");
+    if (io->achieved_goal_stride < 3) return bad(what, "achieved_goal_stride is below 3");
+    if (io->desired_goal_stride < 3) return bad(what, "desired_goal_stride is below 3");
+    return PGX_OK;
 }
 
 }  // namespace
@@ -83,7 +121,7 @@ namespace {
 
 /* y[o] = chain(bias[o]; x[k] * W[o][k], k ascending over K rounded up to 16), optionally ReLU */
 void linear(const float* W, const float* b, const float* x, int K, int out, bool relu, float* y) {
-    const int K16 = (K + 15) & ~15;
+    const int K16 = up16(K);
     for (int o = 0; o < out; o++) {
         float acc = b[o];
         for (int k = 0; k < K; k++) acc = std::fmaf(x[k], W[(size_t)o * K + k], acc);
@@ -92,11 +130,21 @@ void linear(const float* W, const float* b, const float* x, int K, int out, bool
     }
 }
 
-/* x [od + 6] = achieved_goal | desired_goal | observation of row e */
-void stage_x(float* x, const float* obs, const float* achieved_goal, const float* desired_goal, size_t e, int od) {
-    for (int k = 0; k < 3; k++) x[k] = achieved_goal[e * 3 + k];
-    for (int k = 0; k < 3; k++) x[3 + k] = desired_goal[e * 3 + k];
-    for (int k = 0; k < od; k++) x[6 + k] = obs[e * od + k];
+/* x [od + 6 + ad] = achieved_goal | desired_goal | observation | action of row b, each field through its row
+ * stride (floats): (od, 3, 3) for the dense per-env inputs; ad = 0: no action columns */
+void stage_row(float* x, const float* obs, const float* achieved_goal, const float* desired_goal, int s_obs, int s_ag,
+               int s_dg, size_t b, int od, const float* action = nullptr, int s_act = 0, int ad = 0) {
+    for (int k = 0; k < 3; k++) x[k] = achieved_goal[b * s_ag + k];
+    for (int k = 0; k < 3; k++) x[3 + k] = desired_goal[b * s_dg + k];
+    for (int k = 0; k < od; k++) x[6 + k] = obs[b * s_obs + k];
+    for (int k = 0; k < ad; k++) x[6 + od + k] = action[b * s_act + k];
+}
+
+/* the same from a batch launch's io (the action, which the two actors' io only writes, is the caller's to name) */
+template <class Io>
+void stage_row(float* x, const Io* io, size_t b, int od, const float* action = nullptr, int s_act = 0, int ad = 0) {
+    stage_row(x, io->obs, io->achieved_goal, io->desired_goal, io->obs_stride, io->achieved_goal_stride,
+              io->desired_goal_stride, b, od, action, s_act, ad);
 }
 
 /* the nl hidden Linears with their ReLU over x [in_dim], y and z taking turns as output; returns the
@@ -134,22 +182,14 @@ extern "C" int pgx_actor_forward_host(const pgx_actor_config* cfg, const pgx_act
     std::vector<float> x(od + 6), y(PGX_ACTOR_MAX_WIDTH), z(PGX_ACTOR_MAX_WIDTH);
     const int K = cfg->hidden[nl - 1];
     for (int32_t e = 0; e < n; e++) {
-        stage_x(x.data(), obs, achieved_goal, desired_goal, (size_t)e, od);
+        stage_row(x.data(), obs, achieved_goal, desired_goal, od, 3, 3, (size_t)e, od);
         const float* in = hidden_layers(nl, cfg->hidden, w->weight, w->bias, x.data(), od + 6, y.data(), z.data());
         float head[PGX_ACTOR_MAX_ACTION];
         linear(w->weight[nl], w->bias[nl], in, K, A, false, head);
-        for (int d = 0; d < A; d++) {
-            float m = head[d];
-            if (clip > 0.0f) m = m < -clip ? -clip : (m > clip ? clip : m);
-            mean_out[(size_t)e * A + d] = m;
-        }
+        for (int d = 0; d < A; d++) mean_out[(size_t)e * A + d] = clip_to(head[d], clip);
         if (heads == 2 && log_std_out) {
             linear(w->weight[nl + 1], w->bias[nl + 1], in, K, A, false, head);
-            for (int d = 0; d < A; d++) {
-                const float v = head[d];
-                log_std_out[(size_t)e * A + d] =
-                    v < PGX_ACTOR_LOG_STD_MIN ? PGX_ACTOR_LOG_STD_MIN : (v > PGX_ACTOR_LOG_STD_MAX ? PGX_ACTOR_LOG_STD_MAX : v);
-            }
+            for (int d = 0; d < A; d++) log_std_out[(size_t)e * A + d] = clamp_log_std(head[d]);
         }
     }
     return PGX_OK;
@@ -160,28 +200,11 @@ namespace {
 /* what the two action_log_prob launches share: io's pointers and strides, B */
 template <class Io>
 int check_lp_io(const Io* io, int32_t B, int obs_dim, const char* what) {
-    if (!io) return bad(what, "null io");
-    if (!io->obs) return bad(what, "null obs");
-    if (!io->achieved_goal) return bad(what, "null achieved_goal");
-    if (!io->desired_goal) return bad(what, "null desired_goal");
-    if (!io->action) return bad(what, "null action");
+    const int rc = check_rows_ptrs(io, what);
+    if (rc != PGX_OK) return rc;
     if (!io->log_prob) return bad(what, "null log_prob");
-    if (B <= 0) return bad(what, "B must be > 0");
-    if (io->obs_stride < obs_dim) return bad(what, "obs_stride is below obs_dim");
-    if (io->achieved_goal_stride < 3) return bad(what, "achieved_goal_stride is below 3");
-    if (io->desired_goal_stride < 3) return bad(what, "desired_goal_stride is below 3");
-    return PGX_OK;
+    return check_rows_shape(io, B, obs_dim, what);
 }
-
-/* x [od + 6] of row b through the strides */
-template <class Io>
-void stage_x_rows(float* x, const Io* io, size_t b, int od) {
-    for (int k = 0; k < 3; k++) x[k] = io->achieved_goal[b * io->achieved_goal_stride + k];
-    for (int k = 0; k < 3; k++) x[3 + k] = io->desired_goal[b * io->desired_goal_stride + k];
-    for (int k = 0; k < od; k++) x[6 + k] = io->obs[b * io->obs_stride + k];
-}
-
-float clip_to(float m, float clip) { return clip > 0.0f ? (m < -clip ? -clip : (m > clip ? clip : m)) : m; }
 
 /* the epilogues of include/pgx.h, every operation rounded on its own but the one fmaf */
 #pragma clang fp contract(off)
@@ -242,7 +265,7 @@ extern "C" int pgx_actor_log_prob_host(const pgx_actor_config* cfg, const pgx_ac
     const float clip = (float)cfg->clip_mean;
     std::vector<float> x(od + 6), y(PGX_ACTOR_MAX_WIDTH), z(PGX_ACTOR_MAX_WIDTH);
     for (int32_t b = 0; b < n; b++) {
-        stage_x_rows(x.data(), io, (size_t)b, od);
+        stage_row(x.data(), io, (size_t)b, od);
         const float* in = hidden_layers(nl, cfg->hidden, w->weight, w->bias, x.data(), od + 6, y.data(), z.data());
         float mu[PGX_ACTOR_MAX_ACTION], ls[PGX_ACTOR_MAX_ACTION], lp[PGX_ACTOR_MAX_ACTION], c[PGX_ACTOR_MAX_ACTION];
         linear(w->weight[nl], w->bias[nl], in, K, A, false, mu);
@@ -250,8 +273,7 @@ extern "C" int pgx_actor_log_prob_host(const pgx_actor_config* cfg, const pgx_ac
         for (int d = 0; d < A; d++) {
             const size_t o = (size_t)b * A + d;
             const float mean = clip_to(mu[d], clip);
-            const float v = ls[d];
-            const float log_std = v < PGX_ACTOR_LOG_STD_MIN ? PGX_ACTOR_LOG_STD_MIN : (v > PGX_ACTOR_LOG_STD_MAX ? PGX_ACTOR_LOG_STD_MAX : v);
+            const float log_std = clamp_log_std(ls[d]);
             float g, act;
             lp_terms(mean, log_std, io->eps[o], &g, &act, &lp[d], &c[d]);
             io->action[o] = act;
@@ -302,7 +324,7 @@ extern "C" int pgx_ac_forward_host(const pgx_ac_config* cfg, const pgx_ac_weight
         linear(hw, hb, in, hidden[nl - 1], out_dim, false, head);
     };
     for (int32_t e = 0; e < n; e++) {
-        stage_x(x.data(), obs, achieved_goal, desired_goal, (size_t)e, od);
+        stage_row(x.data(), obs, achieved_goal, desired_goal, od, 3, 3, (size_t)e, od);
         float head[PGX_ACTOR_MAX_ACTION];
         if (mean_out) {
             trunk(cfg->n_pi_layers, cfg->pi_hidden, w->pi_weight, w->pi_bias, w->action_net_weight, w->action_net_bias, A,
@@ -347,18 +369,14 @@ extern "C" int pgx_sde_actor_forward_host(const pgx_sde_actor_config* cfg, const
     const float clip = (float)cfg->clip_mean;
     std::vector<float> x(od + 6), y(PGX_ACTOR_MAX_WIDTH), z(PGX_ACTOR_MAX_WIDTH);
     for (int32_t e = 0; e < n; e++) {
-        stage_x(x.data(), obs, achieved_goal, desired_goal, (size_t)e, od);
+        stage_row(x.data(), obs, achieved_goal, desired_goal, od, 3, 3, (size_t)e, od);
         const float* latent = hidden_layers(nl, cfg->hidden, w->weight, w->bias, x.data(), od + 6, y.data(), z.data());
         if (latent_out)
             for (int h = 0; h < H; h++) latent_out[(size_t)e * H + h] = latent[h];
         if (mean_out) {
             float head[PGX_ACTOR_MAX_ACTION];
             linear(w->weight[nl], w->bias[nl], latent, H, A, false, head);
-            for (int d = 0; d < A; d++) {
-                float m = head[d];
-                if (clip > 0.0f) m = m < -clip ? -clip : (m > clip ? clip : m);
-                mean_out[(size_t)e * A + d] = m;
-            }
+            for (int d = 0; d < A; d++) mean_out[(size_t)e * A + d] = clip_to(head[d], clip);
         }
         if (noise_out) {
             const float* E = matrices + (size_t)e * H * A;
@@ -391,7 +409,7 @@ extern "C" int pgx_sde_actor_log_prob_host(const pgx_sde_actor_config* cfg, cons
     for (int l = 0; l <= nl; l++)
         if (!w->weight[l] || !w->bias[l]) return bad(what, "null weight or bias pointer");
     if (!std_ha && !w->log_std) return bad(what, "null std and log_std");
-    const int K16 = (H + 15) & ~15;
+    const int K16 = up16(H);
     std::vector<float> std2((size_t)H * A);
     for (size_t j = 0; j < std2.size(); j++) {
         const float s = std_ha ? std_ha[j] : std::exp(w->log_std[j]);
@@ -400,7 +418,7 @@ extern "C" int pgx_sde_actor_log_prob_host(const pgx_sde_actor_config* cfg, cons
     const float clip = (float)cfg->clip_mean;
     std::vector<float> x(od + 6), y(PGX_ACTOR_MAX_WIDTH), z(PGX_ACTOR_MAX_WIDTH);
     for (int32_t b = 0; b < n; b++) {
-        stage_x_rows(x.data(), io, (size_t)b, od);
+        stage_row(x.data(), io, (size_t)b, od);
         const float* latent = hidden_layers(nl, cfg->hidden, w->weight, w->bias, x.data(), od + 6, y.data(), z.data());
         if (io->latent_out)
             for (int h = 0; h < H; h++) io->latent_out[(size_t)b * H + h] = latent[h];
@@ -437,9 +455,8 @@ extern "C" int pgx_sde_actor_log_prob_host(const pgx_sde_actor_config* cfg, cons
 /* pgx_qc_create's checks (no device call); `what` names the entry point */
 int pgx_qc_check_config(const pgx_qc_config* c, const char* what) {
     if (!c) return bad(what, "null config");
-    if (c->obs_dim <= 0 || c->obs_dim > 4096) return bad(what, "obs_dim must be in 1..4096");
-    if (c->action_dim < 1 || c->action_dim > PGX_ACTOR_MAX_ACTION) return bad(what, "action_dim must be in 1..7");
-    int rc = check_count(what, "n_layers", c->n_layers);
+    int rc = check_dims(what, c->obs_dim, c->action_dim);
+    if (rc == PGX_OK) rc = check_count(what, "n_layers", c->n_layers);
     if (rc == PGX_OK) rc = check_widths(what, "hidden", c->n_layers, c->hidden);
     if (rc != PGX_OK) return rc;
     if (c->n_critics < 1 || c->n_critics > PGX_QC_MAX_CRITICS) return bad(what, "n_critics must be in 1..5");
@@ -452,16 +469,10 @@ int pgx_qc_check_config(const pgx_qc_config* c, const char* what) {
 /* the checks of one launch, pgx_qc_forward's (target false) or pgx_qc_target's, device and host alike */
 int pgx_qc_check_launch(const pgx_qc_config* c, const pgx_qc_io* io, int32_t B, bool target, int32_t n_target,
                         const char* what) {
-    if (!io) return bad(what, "null io");
-    if (!io->obs) return bad(what, "null obs");
-    if (!io->achieved_goal) return bad(what, "null achieved_goal");
-    if (!io->desired_goal) return bad(what, "null desired_goal");
-    if (!io->action) return bad(what, "null action");
+    int rc = check_rows_ptrs(io, what);
+    if (rc != PGX_OK) return rc;
     if (!io->out) return bad(what, "null out");
-    if (B <= 0) return bad(what, "B must be > 0");
-    if (io->obs_stride < c->obs_dim) return bad(what, "obs_stride is below obs_dim");
-    if (io->achieved_goal_stride < 3) return bad(what, "achieved_goal_stride is below 3");
-    if (io->desired_goal_stride < 3) return bad(what, "desired_goal_stride is below 3");
+    if ((rc = check_rows_shape(io, B, c->obs_dim, what)) != PGX_OK) return rc;
     if (io->action_stride < c->action_dim) return bad(what, "action_stride is below action_dim");
     if (!target) return PGX_OK;
     if (!io->reward) return bad(what, "null reward");
@@ -495,10 +506,7 @@ uint32_t qc_key(float v) {
 void qc_row(const pgx_qc_config* cfg, const pgx_qc_weights* w, const pgx_qc_io* io, size_t b, float* x, float* y,
             float* zz, float* out) {
     const int od = cfg->obs_dim, A = cfg->action_dim, nl = cfg->n_layers, nq = cfg->n_quantiles;
-    for (int k = 0; k < 3; k++) x[k] = io->achieved_goal[b * io->achieved_goal_stride + k];
-    for (int k = 0; k < 3; k++) x[3 + k] = io->desired_goal[b * io->desired_goal_stride + k];
-    for (int k = 0; k < od; k++) x[6 + k] = io->obs[b * io->obs_stride + k];
-    for (int k = 0; k < A; k++) x[6 + od + k] = io->action[b * io->action_stride + k];
+    stage_row(x, io, b, od, io->action, io->action_stride, A);
     for (int c = 0; c < cfg->n_critics; c++) {
         const float* in = hidden_layers(nl, cfg->hidden, w->weight[c], w->bias[c], x, od + 6 + A, y, zz);
         linear(w->weight[c][nl], w->bias[c][nl], in, cfg->hidden[nl - 1], nq, false, out + (size_t)c * nq);
@@ -560,9 +568,9 @@ extern "C" int pgx_qc_target_host(const pgx_qc_config* cfg, const pgx_qc_weights
 
 /* floats of one workspace row: x [K16] | per critic A_0 .. A_{nl-1}, dZ_0 .. dZ_nl (widths up to 16) | 16 */
 int64_t pgx_qc_grad_row_floats(const pgx_qc_config* c) {
-    int64_t per_critic = (c->n_quantiles + 15) / 16 * 16;
-    for (int l = 0; l < c->n_layers; l++) per_critic += 2 * ((c->hidden[l] + 15) / 16 * 16);
-    return (c->obs_dim + 6 + c->action_dim + 15) / 16 * 16 + c->n_critics * per_critic + 16;
+    int64_t per_critic = up16(c->n_quantiles);
+    for (int l = 0; l < c->n_layers; l++) per_critic += 2 * up16(c->hidden[l]);
+    return up16(c->obs_dim + 6 + c->action_dim) + c->n_critics * per_critic + 16;
 }
 
 extern "C" int64_t pgx_qc_grad_workspace_floats(const pgx_qc_config* cfg, int32_t B) {
@@ -576,18 +584,12 @@ extern "C" int64_t pgx_qc_grad_workspace_floats(const pgx_qc_config* cfg, int32_
 /* the checks of one pgx_qc_critic_grad launch, device and host alike */
 int pgx_qc_check_grad_launch(const pgx_qc_config* c, const pgx_qc_grad_io* io, int32_t B, int32_t n_target,
                              const char* what) {
-    if (!io) return bad(what, "null io");
-    if (!io->obs) return bad(what, "null obs");
-    if (!io->achieved_goal) return bad(what, "null achieved_goal");
-    if (!io->desired_goal) return bad(what, "null desired_goal");
-    if (!io->action) return bad(what, "null action");
+    int rc = check_rows_ptrs(io, what);
+    if (rc != PGX_OK) return rc;
     if (!io->target_quantiles) return bad(what, "null target_quantiles");
     if (!io->workspace) return bad(what, "null workspace");
     if (!io->loss) return bad(what, "null loss");
-    if (B <= 0) return bad(what, "B must be > 0");
-    if (io->obs_stride < c->obs_dim) return bad(what, "obs_stride is below obs_dim");
-    if (io->achieved_goal_stride < 3) return bad(what, "achieved_goal_stride is below 3");
-    if (io->desired_goal_stride < 3) return bad(what, "desired_goal_stride is below 3");
+    if ((rc = check_rows_shape(io, B, c->obs_dim, what)) != PGX_OK) return rc;
     if (io->action_stride < c->action_dim) return bad(what, "action_stride is below action_dim");
     if (n_target < 1 || n_target > c->n_critics * c->n_quantiles) return bad(what, "n_target must be in 1..n_critics * n_quantiles");
     if (io->workspace_floats < (int64_t)B * pgx_qc_grad_row_floats(c))
@@ -645,8 +647,6 @@ void adam_element(float* p, float g, float* m, float* v, float step_size, float 
 }
 #pragma clang fp contract(on)
 
-int up16(int n) { return (n + 15) / 16 * 16; }
-
 }  // namespace
 
 extern "C" int pgx_qc_critic_grad_host(const pgx_qc_config* cfg, const pgx_qc_weights* w, const pgx_qc_grad_io* io,
@@ -679,10 +679,7 @@ extern "C" int pgx_qc_critic_grad_host(const pgx_qc_config* cfg, const pgx_qc_we
     for (int32_t b = 0; b < B; b++) {
         float* row = ws + (size_t)b * W;
         for (int64_t i = 0; i < W; i++) row[i] = 0.0f;
-        for (int k = 0; k < 3; k++) row[k] = io->achieved_goal[(size_t)b * io->achieved_goal_stride + k];
-        for (int k = 0; k < 3; k++) row[3 + k] = io->desired_goal[(size_t)b * io->desired_goal_stride + k];
-        for (int k = 0; k < od; k++) row[6 + k] = io->obs[(size_t)b * io->obs_stride + k];
-        for (int k = 0; k < A; k++) row[6 + od + k] = io->action[(size_t)b * io->action_stride + k];
+        stage_row(row, io, (size_t)b, od, io->action, io->action_stride, A);
         float q[PGX_QC_MAX_QUANTILES];
         float rl = 0.0f;
         for (int c = 0; c < nc; c++) {

@@ -1,7 +1,8 @@
 /*
  * pgx_mlp.h -- the device side the policy units (pgx_actor.hip, pgx_actor_critic.hip, pgx_sde_actor.hip,
- * pgx_quantile_critic.hip) share: the plan of one stack of Linears, the feature staging their forward kernels open with
- * (dense per env, or through row strides for a batch), the ordered sums of a batch row's log-probability, one
+ * pgx_quantile_critic.hip) share: the plan of one stack of Linears, the feature staging their kernels open with
+ * (stage_features dense per env; stage_rows through row strides for every batch launch, with or without action
+ * columns), the ordered sums of a batch row's log-probability, one
  * Linear over a workgroup's env tile as v_mfma_f32_16x16x4_f32 on activations kept in LDS, the loop that
  * runs a stack through two LDS regions, the Gaussian draw from the Philox stream, the advance of a
  * device-resident noise word, and the kernel that packs torch-layout weights for the Linear.  Arithmetic
@@ -53,21 +54,23 @@ __device__ __forceinline__ void stage_features(float* lds, const float* obs, con
     }
 }
 
-/* the same for the rows of a batch, each field read through its own row stride (floats): a HER batch's
- * rows are read where they lie */
+/* the same for the rows of a batch, each field read through its own row stride (floats), so a HER batch's
+ * rows are read where they lie: achieved_goal | desired_goal | observation | action (ad columns; 0 and NULL:
+ * none), +0 past od + 6 + ad and past row B */
 template <int MT>
-__device__ __forceinline__ void stage_features_rows(float* lds, const float* obs, const float* achieved_goal,
-                                                    const float* desired_goal, int s_obs, int s_ag, int s_dg, int row0,
-                                                    int B, int od, int K0, int S, int tid) {
-    const int in_dim = od + 6;
+__device__ __forceinline__ void stage_rows(float* lds, const float* obs, const float* achieved_goal,
+                                           const float* desired_goal, const float* action, int s_obs, int s_ag, int s_dg,
+                                           int s_act, int row0, int B, int od, int ad, int K0, int S, int tid) {
+    const int K = od + 6 + ad;
     for (int idx = tid; idx < MT * 16 * K0; idx += THREADS) {
         const int r = idx / K0, k = idx - r * K0;
         const size_t b = (size_t)(row0 + r);
         float v = 0.0f;
-        if (row0 + r < B && k < in_dim) {
+        if (row0 + r < B && k < K) {
             if (k < 3) v = achieved_goal[b * s_ag + k];
             else if (k < 6) v = desired_goal[b * s_dg + (k - 3)];
-            else v = obs[b * s_obs + (k - 6)];
+            else if (k < 6 + od) v = obs[b * s_obs + (k - 6)];
+            else v = action[b * s_act + (k - 6 - od)];
         }
         lds[r * S + k] = v;
     }

@@ -1,7 +1,8 @@
 /*
  * pgx_policy.h -- the host side the policy units (pgx_actor.hip, pgx_actor_critic.hip, pgx_sde_actor.hip,
- * pgx_quantile_critic.hip) share: planning a stack of Linears, the tile choice, the handle's one device allocation, copy-and-pack
- * of a Linear, the noise word's read and write, the launch of a forward kernel in its tile size.  The
+ * pgx_quantile_critic.hip) share: planning a stack of Linears, the tile choice (choose_tile for a launch, max_tile
+ * for what fits at all, set_tile_lds for a batch kernel pair's dynamic LDS), the handle's one device allocation,
+ * copy-and-pack of a Linear, the noise word's read and write, the launch of a kernel in its tile size.  The
  * device side: pgx_mlp.h.  Everything here has internal linkage: each unit compiles its own copy.
  */
 #ifndef PGX_POLICY_H
@@ -70,6 +71,24 @@ int choose_tile(int n_envs, const char* env_var, F lds_bytes, int two_from = 409
         if (const char* t = std::getenv(env_var)) mt = std::atoi(t) == 32 ? 2 : 1;
     if (lds_bytes(mt) > LDS_LIMIT) mt = 1;
     return lds_bytes(mt) > LDS_LIMIT ? 0 : mt;
+}
+
+/* the largest tile lds_bytes admits, whatever the batch and the environment say: 2, 1, or 0 for none */
+template <class F>
+int max_tile(F lds_bytes) {
+    return choose_tile(17, nullptr, lds_bytes, 17);
+}
+
+/* The dynamic LDS of a batch launch's kernel pair, k1 (16 rows) and k2 (32), each for its own tile: 16 rows
+ * where they fit, 32 where they do.  False: the runtime refused. */
+template <class K, class F>
+bool set_tile_lds(K k1, K k2, F lds_bytes) {
+    const int mt_max = max_tile(lds_bytes);
+    bool ok = true;
+    for (int mt = 1; mt <= mt_max; mt++)
+        ok = ok && hipFuncSetAttribute((const void*)(mt == 2 ? k2 : k1), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds_bytes(mt)) == hipSuccess;
+    return ok;
 }
 
 /* The handle's one device allocation, zeroed: n regions of bytes[i], region i at the 256-aligned ptr[i]

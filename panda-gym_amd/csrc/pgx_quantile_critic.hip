@@ -50,26 +50,6 @@ struct QcArgs {
     MlpPlan plan;                 /* one critic's Linears, offsets from the critic's first float */
 };
 
-/* features of the workgroup's MT x 16 rows into lds (row stride S0), K0 columns each: achieved_goal |
- * desired_goal | observation | action through their row strides, +0 past K and past row B */
-template <int MT, class Io>
-__device__ __forceinline__ void stage_rows(float* lds, const Io& io, int row0, int B, int od, int ad, int K0,
-                                           int S0, int tid) {
-    const int K = od + 6 + ad;
-    for (int idx = tid; idx < MT * 16 * K0; idx += THREADS) {
-        const int r = idx / K0, k = idx - r * K0;
-        const size_t b = (size_t)(row0 + r);
-        float v = 0.0f;
-        if (row0 + r < B && k < K) {
-            if (k < 3) v = io.achieved_goal[b * io.achieved_goal_stride + k];
-            else if (k < 6) v = io.desired_goal[b * io.desired_goal_stride + (k - 3)];
-            else if (k < 6 + od) v = io.obs[b * io.obs_stride + (k - 6)];
-            else v = io.action[b * io.action_stride + (k - 6 - od)];
-        }
-        lds[r * S0 + k] = v;
-    }
-}
-
 /* the rows' quantiles of every critic of the set at `params` into the pool region: critic c's quantile q
  * of row r at lds[ROWS * R0 + r * SP + c * HT * 16 + q]; ends behind a barrier */
 template <int MT>
@@ -77,7 +57,8 @@ __device__ __forceinline__ void pooled_quantiles(float* lds, const QcArgs& a, co
                                                  int row0, int B, int tid) {
     constexpr int ROWS = MT * 16;
     const int lane = tid & 63, wave = tid >> 6;
-    stage_rows<MT>(lds, io, row0, B, a.od, a.ad, a.plan.nkb[0] * 16, a.S0, tid);
+    stage_rows<MT>(lds, io.obs, io.achieved_goal, io.desired_goal, io.action, io.obs_stride, io.achieved_goal_stride,
+                   io.desired_goal_stride, io.action_stride, row0, B, a.od, a.ad, a.plan.nkb[0] * 16, a.S0, tid);
     __syncthreads();
     const int ping = ROWS * a.S0, pong = ping + ROWS * a.S, pool = ROWS * a.R0;
     const int nl = a.plan.n_linear - 1;
@@ -336,7 +317,8 @@ __global__ __launch_bounds__(THREADS) void qc_grad_rows_kernel(QcArgs a, QcGradA
     const int row0 = blockIdx.x * ROWS;
     const int K16 = a.plan.nkb[0] * 16, nl = a.plan.n_linear - 1, Q16 = a.HT * 16, W = g.W;
     float* ws = io.workspace;
-    stage_rows<MT>(lds, io, row0, B, a.od, a.ad, K16, a.S0, tid);
+    stage_rows<MT>(lds, io.obs, io.achieved_goal, io.desired_goal, io.action, io.obs_stride, io.achieved_goal_stride,
+                   io.desired_goal_stride, io.action_stride, row0, B, a.od, a.ad, K16, a.S0, tid);
     __syncthreads();
     store_plane<MT>(lds, 0, a.S0, K16, ws, W, 0, row0, B, tid);
     const int ping = ROWS * a.S0, pong = ping + ROWS * g.S, pool = ROWS * (a.S0 + 2 * g.S);
@@ -531,19 +513,28 @@ struct pgx_qc {
 
     size_t set_floats() const { return (size_t)cfg.n_critics * a.critic_floats; }
     size_t set_plain() const { return (size_t)cfg.n_critics * critic_plain; }
-    size_t lds_need(int mt) const { return (size_t)mt * 16 * (a.R0 + a.SP) * 4; }
-    int tile(int B) const {
-        return choose_tile(B, "PGX_QC_TILE", [this](int mt) { return lds_need(mt); }, 17);
-    }
-    size_t grad_lds_need(int mt) const { return (size_t)mt * 16 * (a.S0 + 2 * g.S + a.SP) * 4; }
-    int grad_tile(int B) const {
-        return choose_tile(B, "PGX_QC_TILE", [this](int mt) { return grad_lds_need(mt); }, 17);
-    }
+    /* LDS floats per row of a forward / target launch, and of the gradient's rows launch */
+    int fwd_row() const { return a.R0 + a.SP; }
+    int grad_row() const { return a.S0 + 2 * g.S + a.SP; }
 };
 
 namespace {
 
-int bad_which(const char* what) { return fail(PGX_E_INVALID, what, "which must be PGX_QC_ONLINE or PGX_QC_TARGET"); }
+/* the dynamic LDS of mt x 16 rows of row_floats each, as a function of mt */
+auto lds_need(int row_floats) {
+    return [row_floats](int mt) { return (size_t)mt * 16 * row_floats * 4; };
+}
+
+/* row tiles of 16 per workgroup of a launch over B rows: 32 rows from 17 on, where they fit the LDS */
+int row_tile(int B, int row_floats) { return choose_tile(B, "PGX_QC_TILE", lds_need(row_floats), 17); }
+
+/* the opening of the entry points that take a set */
+int check_which(const pgx_qc* h, int which, const char* what) {
+    if (!h) return fail(PGX_E_INVALID, what, "null handle");
+    if (which != PGX_QC_ONLINE && which != PGX_QC_TARGET)
+        return fail(PGX_E_INVALID, what, "which must be PGX_QC_ONLINE or PGX_QC_TARGET");
+    return PGX_OK;
+}
 
 /* packs set `which` from its plain copy, or (w != NULL) copies w's parameters there first */
 bool pack_set(pgx_qc* h, int which, const pgx_qc_weights* w, hipStream_t st) {
@@ -553,8 +544,7 @@ bool pack_set(pgx_qc* h, int which, const pgx_qc_weights* w, hipStream_t st) {
         float* plain = h->plain + which * h->set_plain() + c * h->critic_plain;
         float* packed = h->params + which * h->set_floats() + (size_t)c * h->a.critic_floats;
         for (int l = 0; l <= nl; l++) {
-            int o, in;
-            linear_dims(h->cfg.obs_dim + 6 + h->cfg.action_dim, h->cfg.hidden, nl, h->cfg.n_quantiles, l, &o, &in);
+            const int o = h->g.out[l], in = h->g.in[l];
             float* pw = plain + h->plain_w[l];
             float* pb = plain + h->plain_b[l];
             const bool ok = w ? pack_linear(w->weight[c][l], w->bias[c][l], pw, pb, o, in, packed + p.woff[l],
@@ -651,7 +641,7 @@ int pgx_qc_create(const pgx_qc_config* cfg, int device, pgx_qc_handle* out) {
         }
     }
     g.CW = 2 * g.sumH16 + a.HT * 16;
-    const int mt_max = choose_tile(17, nullptr, [h](int mt) { return h->lds_need(mt); }, 17);
+    const int mt_max = max_tile(lds_need(h->fwd_row()));
     if (mt_max == 0) {
         delete h;
         return pgx_set_error(PGX_E_UNSUPPORTED, "pgx_qc_create: obs_dim too wide for the features in LDS");
@@ -661,7 +651,7 @@ int pgx_qc_create(const pgx_qc_config* cfg, int device, pgx_qc_handle* out) {
     const int rc = create_blob("pgx_qc_create", device, bytes, 2, ptr,
                                {(const void*)qc_forward_kernel<1>, (const void*)qc_forward_kernel<2>,
                                 (const void*)qc_target_kernel<1>, (const void*)qc_target_kernel<2>},
-                               h->lds_need(mt_max));
+                               lds_need(h->fwd_row())(mt_max));
     if (rc != PGX_OK) {
         delete h;
         return rc;
@@ -682,9 +672,8 @@ void pgx_qc_destroy(pgx_qc_handle h) {
 
 int pgx_qc_set_weights(pgx_qc_handle h, int32_t which, const pgx_qc_weights* w, void* stream) {
     const char* what = "pgx_qc_set_weights";
-    if (!h) return fail(PGX_E_INVALID, what, "null handle");
-    if (which != PGX_QC_ONLINE && which != PGX_QC_TARGET) return bad_which(what);
-    const int rc = pgx_qc_check_weights(&h->cfg, w, what);
+    int rc = check_which(h, which, what);
+    if (rc == PGX_OK) rc = pgx_qc_check_weights(&h->cfg, w, what);
     if (rc != PGX_OK) return rc;
     if (!pack_set(h, which, w, (hipStream_t)stream)) return fail(PGX_E_HIP, what, "copy failed");
     if (which == PGX_QC_ONLINE) pack_transposed(h, (hipStream_t)stream);
@@ -693,36 +682,23 @@ int pgx_qc_set_weights(pgx_qc_handle h, int32_t which, const pgx_qc_weights* w, 
 
 int pgx_qc_get_weights(pgx_qc_handle h, int32_t which, const pgx_qc_weights* w, void* stream) {
     const char* what = "pgx_qc_get_weights";
-    if (!h) return fail(PGX_E_INVALID, what, "null handle");
-    if (which != PGX_QC_ONLINE && which != PGX_QC_TARGET) return bad_which(what);
-    const int rc = pgx_qc_check_weights(&h->cfg, w, what);
+    int rc = check_which(h, which, what);
+    if (rc == PGX_OK) rc = pgx_qc_check_weights(&h->cfg, w, what);
     if (rc != PGX_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int nl = h->cfg.n_layers;
-    for (int c = 0; c < h->cfg.n_critics; c++) {
-        const float* plain = h->plain + which * h->set_plain() + c * h->critic_plain;
-        for (int l = 0; l <= nl; l++) {
-            int o, in;
-            linear_dims(h->cfg.obs_dim + 6 + h->cfg.action_dim, h->cfg.hidden, nl, h->cfg.n_quantiles, l, &o, &in);
-            if (hipMemcpyAsync(const_cast<float*>(w->weight[c][l]), plain + h->plain_w[l], (size_t)o * in * 4,
-                               hipMemcpyDefault, st) != hipSuccess ||
-                hipMemcpyAsync(const_cast<float*>(w->bias[c][l]), plain + h->plain_b[l], (size_t)o * 4, hipMemcpyDefault,
-                               st) != hipSuccess)
-                return fail(PGX_E_HIP, what, "copy failed");
-        }
-    }
+    if (!copy_plain(h, h->plain + which * h->set_plain(), w, true, st)) return fail(PGX_E_HIP, what, "copy failed");
     return hipStreamSynchronize(st) == hipSuccess ? PGX_OK : fail(PGX_E_HIP, what, "synchronise failed");
 }
 
 int pgx_qc_forward(pgx_qc_handle h, int32_t which, const pgx_qc_io* io, int32_t B, void* stream) {
     const char* what = "pgx_qc_forward";
-    if (!h) return fail(PGX_E_INVALID, what, "null handle");
-    if (which != PGX_QC_ONLINE && which != PGX_QC_TARGET) return bad_which(what);
-    const int rc = pgx_qc_check_launch(&h->cfg, io, B, false, 0, what);
+    int rc = check_which(h, which, what);
+    if (rc == PGX_OK) rc = pgx_qc_check_launch(&h->cfg, io, B, false, 0, what);
     if (rc != PGX_OK) return rc;
-    const int mt = h->tile(B);
+    const int mt = row_tile(B, h->fwd_row());
     const float* params = h->params + which * h->set_floats();
-    launch_tiles(qc_forward_kernel<1>, qc_forward_kernel<2>, mt, B, h->lds_need(mt), stream, h->a, params, *io, B);
+    launch_tiles(qc_forward_kernel<1>, qc_forward_kernel<2>, mt, B, lds_need(h->fwd_row())(mt), stream, h->a, params, *io,
+                 B);
     return hipGetLastError() == hipSuccess ? PGX_OK : fail(PGX_E_HIP, what, "launch failed");
 }
 
@@ -731,9 +707,9 @@ int pgx_qc_target(pgx_qc_handle h, const pgx_qc_io* io, int32_t B, int32_t n_tar
     if (!h) return fail(PGX_E_INVALID, what, "null handle");
     const int rc = pgx_qc_check_launch(&h->cfg, io, B, true, n_target, what);
     if (rc != PGX_OK) return rc;
-    const int mt = h->tile(B);
+    const int mt = row_tile(B, h->fwd_row());
     const float* params = h->params + PGX_QC_TARGET * h->set_floats();
-    launch_tiles(qc_target_kernel<1>, qc_target_kernel<2>, mt, B, h->lds_need(mt), stream, h->a, params, *io, B,
+    launch_tiles(qc_target_kernel<1>, qc_target_kernel<2>, mt, B, lds_need(h->fwd_row())(mt), stream, h->a, params, *io, B,
                  n_target);
     return hipGetLastError() == hipSuccess ? PGX_OK : fail(PGX_E_HIP, what, "launch failed");
 }
@@ -766,13 +742,13 @@ int pgx_qc_init_training(pgx_qc_handle h, double beta1, double beta2, double eps
     if (rc0 != PGX_OK) return rc0;
     const size_t n = h->set_plain();
     if (!h->grad) {
-        const int mt_max = choose_tile(17, nullptr, [h](int mt) { return h->grad_lds_need(mt); }, 17);
+        const int mt_max = max_tile(lds_need(h->grad_row()));
         if (mt_max == 0) return fail(PGX_E_UNSUPPORTED, what, "the critic is too wide for the backward's rows in LDS");
         const size_t bytes[6] = {n * 4, n * 4, n * 4, (size_t)h->cfg.n_critics * h->g.critic_pt * 4 + 4, 2 * 4, 8};
         void* ptr[6];
         const int rc = create_blob(what, h->device, bytes, 6, ptr,
                                    {(const void*)qc_grad_rows_kernel<1>, (const void*)qc_grad_rows_kernel<2>},
-                                   h->grad_lds_need(mt_max));
+                                   lds_need(h->grad_row())(mt_max));
         if (rc != PGX_OK) return rc;
         h->grad = (float*)ptr[0];
         h->exp_avg = (float*)ptr[1];
@@ -802,8 +778,8 @@ int pgx_qc_critic_grad(pgx_qc_handle h, const pgx_qc_grad_io* io, int32_t B, int
     QcGradArgs g = h->g;
     g.nt = n_target;
     g.inv_count = pgx_qc_inv_count(&h->cfg, B, n_target);
-    const int mt = h->grad_tile(B);
-    launch_tiles(qc_grad_rows_kernel<1>, qc_grad_rows_kernel<2>, mt, B, h->grad_lds_need(mt), stream, h->a, g,
+    const int mt = row_tile(B, h->grad_row());
+    launch_tiles(qc_grad_rows_kernel<1>, qc_grad_rows_kernel<2>, mt, B, lds_need(h->grad_row())(mt), stream, h->a, g,
                  (const float*)h->params, (const float*)h->pt, *io, B);
     const int blocks = h->cfg.n_critics * g.tile0[h->cfg.n_layers + 1] + 1;
     hipLaunchKernelGGL(qc_wgrad_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream, h->a, g, io->workspace, h->grad,

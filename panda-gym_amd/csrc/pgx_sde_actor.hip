@@ -168,8 +168,8 @@ __global__ __launch_bounds__(THREADS) void sde_lp_kernel(SdeArgs a, SdeBatch bt,
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int S = a.S, B = a.n, A = a.ad, H = a.H;
     const int row0 = blockIdx.x * ROWS;
-    stage_features_rows<MT>(lds, io.obs, io.achieved_goal, io.desired_goal, io.obs_stride, io.achieved_goal_stride,
-                            io.desired_goal_stride, row0, B, a.od, a.plan.nkb[0] * 16, S, tid);
+    stage_rows<MT>(lds, io.obs, io.achieved_goal, io.desired_goal, nullptr, io.obs_stride, io.achieved_goal_stride,
+                   io.desired_goal_stride, 0, row0, B, a.od, 0, a.plan.nkb[0] * 16, S, tid);
     __syncthreads();
     const int lm = a.plan.n_linear - 1;
     const int in_off = run_linears<MT>(lds, a.params, a.plan, lm, true, 0, S, ROWS * S, 0, S, lane, wave);
@@ -422,13 +422,7 @@ int pgx_sde_actor_create(const pgx_sde_actor_config* cfg, int device, pgx_sde_ac
     h->bt.P2 = (float*)ptr[5];
     h->bt.Eb = h->bt.P2 + n_p2;
     h->bt.std2 = h->bt.Eb + n_std;
-    /* the batch kernels' dynamic LDS: 16 rows always fit, 32 where they do */
-    bool ok = hipFuncSetAttribute((const void*)sde_lp_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)h->lds_need(1)) == hipSuccess;
-    if (choose_tile(17, nullptr, [h](int mt) { return h->lds_need(mt); }, 17) == 2)
-        ok = ok && hipFuncSetAttribute((const void*)sde_lp_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)h->lds_need(2)) == hipSuccess;
-    if (!ok) {
+    if (!set_tile_lds(sde_lp_kernel<1>, sde_lp_kernel<2>, lds_need)) {
         (void)hipFree(h->params);
         delete h;
         return pgx_set_error(PGX_E_HIP, "pgx_sde_actor_create: device setup failed");

@@ -107,14 +107,16 @@ class QuantileCritic(Policy):
         return which
 
     def _weights_struct(self, ws, bs) -> abi.PgxQcWeights:
+        """``ws`` / ``bs``: every critic's Linears in ``_names`` order, tensors or numpy arrays."""
+        p = lambda x: x.data_ptr() if torch.is_tensor(x) else x.ctypes.data  # noqa: E731
         w = abi.PgxQcWeights()
         for i, (x, y) in enumerate(zip(ws, bs)):
             c, l = divmod(i, self._n_linear)
-            w.weight[c][l], w.bias[c][l] = x, y
+            w.weight[c][l], w.bias[c][l] = p(x), p(y)
         return w
 
     def _set_struct(self, which: str) -> abi.PgxQcWeights:
-        return self._weights_struct([t.data_ptr() for t in self._ws[which]], [t.data_ptr() for t in self._bs[which]])
+        return self._weights_struct(self._ws[which], self._bs[which])
 
     def _push(self) -> None:
         for s in self._loading:
@@ -176,24 +178,13 @@ class QuantileCritic(Policy):
             self._loading = SETS
 
     # --------------------------------------------------------------- launches
-    def _io(self, obs: Dict[str, Any], actions, B: Optional[int] = None):
-        o, so = self._field(obs["observation"], self.obs_dim, B, "observation")
-        B = int(o.shape[0])
-        ag, sag = self._field(obs["achieved_goal"], 3, B, "achieved_goal")
-        dg, sdg = self._field(obs["desired_goal"], 3, B, "desired_goal")
-        a, sa = self._field(actions, self.action_dim, B, "actions")
+    def _io(self, obs: Dict[str, Any], actions):
         io = abi.PgxQcIo()
-        io.obs, io.achieved_goal, io.desired_goal, io.action = o.data_ptr(), ag.data_ptr(), dg.data_ptr(), a.data_ptr()
-        io.obs_stride, io.achieved_goal_stride, io.desired_goal_stride, io.action_stride = so, sag, sdg, sa
-        return io, B, [o, ag, dg, a]
+        B, keep = self._rows_into(io, obs, actions)
+        return io, B, keep
 
     def _out(self, out, B: int, width: int) -> "torch.Tensor":
-        if out is None:
-            return torch.empty((B, width), dtype=torch.float32, device=self.device)
-        if not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != self.device \
-                or not out.is_contiguous() or out.dim() != 2 or out.shape[0] < B or out.shape[1] != width:
-            raise ValueError(f"out must be a contiguous f32 [>= {B}, {width}] tensor on {self.device}")
-        return out
+        return self._f32_out(out, B, (width,), f"out must be a contiguous f32 [>= {B}, {width}] tensor on {self.device}")
 
     def critic(self, obs: Dict[str, Any], actions, target: bool = False, out=None) -> "torch.Tensor":
         """Quantiles [B, n_critics, n_quantiles] of ``critic(obs, actions)`` (``target``: of
@@ -242,9 +233,7 @@ class QuantileCritic(Policy):
         """``td_target`` on a HER batch (``buf.alloc_batch`` / ``buf.sample_into``): ``next_obs``,
         ``next_achieved_goal``, ``next_desired_goal``, ``reward`` and ``done`` are read from ``batch["rows"]``
         in place."""
-        nxt = {"observation": batch["next_obs"], "achieved_goal": batch["next_achieved_goal"],
-               "desired_goal": batch["next_desired_goal"]}
-        return self.td_target(nxt, next_actions, next_log_prob, batch["reward"], batch["done"], ent_coef, out=out)
+        return self.td_target(self._batch_obs(batch, True), next_actions, next_log_prob, batch["reward"], batch["done"], ent_coef, out=out)
 
     def polyak_update(self, tau: float) -> None:
         """SB3's ``polyak_update(critic.parameters(), critic_target.parameters(), tau)`` on the handle's
@@ -263,22 +252,15 @@ class QuantileCritic(Policy):
 
     # ------------------------------------------------------------ host models
     def _host_io(self, obs: Dict[str, Any], actions):
-        o, n = self._host_obs(obs)
-        a = np.ascontiguousarray(actions.cpu().numpy() if torch.is_tensor(actions) else actions, dtype=np.float32)
-        if o["observation"].shape != (n, self.obs_dim) or a.shape != (n, self.action_dim):
-            raise ValueError(f"expected observation [n, {self.obs_dim}] and actions [n, {self.action_dim}]")
         io = abi.PgxQcIo()
-        io.obs, io.achieved_goal, io.desired_goal, io.action = (abi.ptr(o["observation"]), abi.ptr(o["achieved_goal"]),
-                                                                abi.ptr(o["desired_goal"]), abi.ptr(a))
-        io.obs_stride, io.achieved_goal_stride, io.desired_goal_stride, io.action_stride = self.obs_dim, 3, 3, \
-            self.action_dim
-        return io, n, [o, a]
+        n, keep = self._host_rows_into(io, obs, actions)
+        return io, n, keep
 
     def _host_set(self, which: str):
         self._pull_target()
         ws = [np.ascontiguousarray(t.cpu().numpy()) for t in self._ws[which]]
         bs = [np.ascontiguousarray(t.cpu().numpy()) for t in self._bs[which]]
-        return self._weights_struct([x.ctypes.data for x in ws], [x.ctypes.data for x in bs]), [ws, bs]
+        return self._weights_struct(ws, bs), [ws, bs]
 
     def forward_host(self, obs: Dict[str, Any], actions, target: bool = False) -> np.ndarray:
         """Quantiles [n, n_critics, n_quantiles] numpy f32 from the library's host model of the kernel's
@@ -380,14 +362,11 @@ class QuantileCritic(Policy):
         one-float f32 device tensor to fill instead of a new one)."""
         self._need_device()
         io = abi.PgxQcGradIo()
-        qio, B, keep = self._io(obs, actions)
-        for f in ("obs", "achieved_goal", "desired_goal", "action"):
-            setattr(io, f, getattr(qio, f))
-            setattr(io, f + "_stride", getattr(qio, f + "_stride"))
-        tq = target_quantiles
-        if not torch.is_tensor(tq) or tq.dtype != torch.float32 or tq.device != self.device or tq.dim() != 2 \
-                or tq.shape[0] < B or not tq.is_contiguous():
-            raise ValueError(f"target_quantiles must be a contiguous f32 [>= {B}, n_target] tensor on {self.device}")
+        B, keep = self._rows_into(io, obs, actions)
+        what = f"target_quantiles must be a contiguous f32 [>= {B}, n_target] tensor on {self.device}"
+        if target_quantiles is None:   # (an input: there is no new one to make)
+            raise ValueError(what)
+        tq = self._f32_out(target_quantiles, B, (None,), what)
         ws = workspace
         if not torch.is_tensor(ws) or ws.dtype != torch.float32 or ws.device != self.device or not ws.is_contiguous():
             raise ValueError(f"workspace must be a contiguous f32 tensor on {self.device} (alloc_workspace)")
@@ -419,7 +398,7 @@ class QuantileCritic(Policy):
         ``qf{i}.{0,2,4}.weight|bias`` (copies)."""
         self._need_device()
         ws, bs = self._like_online()
-        w = self._weights_struct([t.data_ptr() for t in ws], [t.data_ptr() for t in bs])
+        w = self._weights_struct(ws, bs)
         self._call("get_grads", self._h, C.byref(w), self._stream())
         return self._named(ws, bs)
 
@@ -447,8 +426,7 @@ class QuantileCritic(Policy):
                     "exp_avg_sq": {k: torch.as_tensor(x.copy()) for k, x in st["exp_avg_sq"].items()},
                     "step": st["step"], "betas": self._opt[:2], "eps": self._opt[2]}
         m, v = self._like_online(), self._like_online()
-        sm = self._weights_struct([t.data_ptr() for t in m[0]], [t.data_ptr() for t in m[1]])
-        sv = self._weights_struct([t.data_ptr() for t in v[0]], [t.data_ptr() for t in v[1]])
+        sm, sv = self._weights_struct(*m), self._weights_struct(*v)
         step = C.c_uint64(0)
         self._call("get_opt_state", self._h, C.byref(sm), C.byref(sv), C.byref(step), self._stream())
         return {"exp_avg": self._named(*m), "exp_avg_sq": self._named(*v), "step": int(step.value),
@@ -467,8 +445,7 @@ class QuantileCritic(Policy):
         if self._h is None:
             self._cpu_state = {"exp_avg": self._named(*m), "exp_avg_sq": self._named(*v), "step": step}
             return
-        sm = self._weights_struct([x.ctypes.data for x in m[0]], [x.ctypes.data for x in m[1]])
-        sv = self._weights_struct([x.ctypes.data for x in v[0]], [x.ctypes.data for x in v[1]])
+        sm, sv = self._weights_struct(*m), self._weights_struct(*v)
         self._call("set_opt_state", self._h, C.byref(sm), C.byref(sv), C.c_uint64(step), self._stream())
         torch.cuda.synchronize(self.device)   # (the copies read the numpy arrays above)
 
@@ -476,11 +453,8 @@ class QuantileCritic(Policy):
         """``(loss, grads)`` -- a numpy f32 scalar and numpy arrays under the parameters' key names -- from the
         library's host model of ``critic_loss_backward`` on the online set; ``return_debug``: also the
         ``quantiles`` / ``dq`` / ``dz`` planes.  A test oracle."""
-        qio, n, keep = self._host_io(obs, actions)
         io = abi.PgxQcGradIo()
-        for f in ("obs", "achieved_goal", "desired_goal", "action"):
-            setattr(io, f, getattr(qio, f))
-            setattr(io, f + "_stride", getattr(qio, f + "_stride"))
+        n, keep = self._host_rows_into(io, obs, actions)
         tq = np.ascontiguousarray(target_quantiles.detach().cpu().numpy() if torch.is_tensor(target_quantiles)
                                   else target_quantiles, dtype=np.float32)
         if tq.ndim != 2 or tq.shape[0] != n:
@@ -494,7 +468,7 @@ class QuantileCritic(Policy):
         io.quantiles_out, io.dq_out, io.dz_out = abi.ptr(dbg["quantiles"]), abi.ptr(dbg["dq"]), abi.ptr(dbg["dz"])
         gw = [np.zeros(tuple(t.shape), np.float32) for t in self._ws["online"]]
         gb = [np.zeros(tuple(t.shape), np.float32) for t in self._bs["online"]]
-        g = self._weights_struct([x.ctypes.data for x in gw], [x.ctypes.data for x in gb])
+        g = self._weights_struct(gw, gb)
         self._call("critic_grad_host", C.byref(self._cfg), C.byref(w), C.byref(io), n, int(tq.shape[1]), C.byref(g))
         out = (loss[0], self._named(gw, gb))
         return out + (dbg,) if return_debug else out
@@ -517,7 +491,7 @@ class QuantileCritic(Policy):
         m = self._unnamed(zeros if state is None else state["exp_avg"], "adam_step_host: exp_avg")
         v = self._unnamed(zeros if state is None else state["exp_avg_sq"], "adam_step_host: exp_avg_sq")
         step = C.c_uint64(0 if state is None else int(state["step"]))
-        structs = [self._weights_struct([x.ctypes.data for x in a[0]], [x.ctypes.data for x in a[1]]) for a in (p, g, m, v)]
+        structs = [self._weights_struct(*a) for a in (p, g, m, v)]
         self._call("adam_step_host", C.byref(self._cfg), *[C.byref(x) for x in structs], C.byref(step), C.c_double(float(lr)),
                    C.c_double(b1), C.c_double(b2), C.c_double(e))
         return self._named(*p), {"exp_avg": self._named(*m), "exp_avg_sq": self._named(*v), "step": int(step.value)}

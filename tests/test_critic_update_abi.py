@@ -286,6 +286,37 @@ def test_launch_checks_refuse_without_a_device(field, value, words):
     assert b"pgx_qc_critic_grad_host" in msg and words in msg, msg
 
 
+def test_launch_checks_keep_their_order():
+    """Every field bad at once: the first of the ladder wins, and as each is mended, the next.  The pointers and
+    the strides at the ladder's two ends are checked by code the other batch launches share, this launch's own
+    pointers in between: the winner for any set of bad fields stays the one it was."""
+    lib = _native.load()
+    cfg, w, io, n, n_target, g, keep = _grad_call()
+    ladder = [("obs", None, b"null obs"), ("achieved_goal", None, b"null achieved_goal"),
+              ("desired_goal", None, b"null desired_goal"), ("action", None, b"null action"),
+              ("target_quantiles", None, b"null target_quantiles"), ("workspace", None, b"null workspace"),
+              ("loss", None, b"null loss"), ("B", 0, b"B must be > 0"), ("obs_stride", 5, b"obs_stride"),
+              ("achieved_goal_stride", 2, b"achieved_goal_stride"), ("desired_goal_stride", 0, b"desired_goal_stride"),
+              ("action_stride", 2, b"action_stride"), ("n_target", 0, b"n_target"),
+              ("workspace_floats", 0, b"workspace_floats is below")]
+    call = {"B": n, "n_target": n_target}
+    good = {f: call[f] if f in call else getattr(io, f) for f, _, _ in ladder}
+
+    def put(field, value):
+        if field in call:
+            call[field] = value
+        else:
+            setattr(io, field, value)
+
+    for field, value, _ in ladder:
+        put(field, value)
+    for field, _, words in ladder:
+        rc = lib.pgx_qc_critic_grad_host(C.byref(cfg), C.byref(w), C.byref(io), call["B"], call["n_target"], C.byref(g))
+        assert rc == abi.PGX_E_INVALID and words in lib.pgx_last_error(), (field, lib.pgx_last_error())
+        put(field, good[field])
+    assert lib.pgx_qc_critic_grad_host(C.byref(cfg), C.byref(w), C.byref(io), n, n_target, C.byref(g)) == abi.PGX_OK
+
+
 @pytest.mark.parametrize("b1,b2,eps,word", [(1.0, 0.999, 1e-8, b"beta1"), (-0.1, 0.999, 1e-8, b"beta1"),
                                             (0.9, 1.0, 1e-8, b"beta2"), (0.9, float("nan"), 1e-8, b"beta2"),
                                             (0.9, 0.999, 0.0, b"eps"), (0.9, 0.999, float("inf"), b"eps")])
