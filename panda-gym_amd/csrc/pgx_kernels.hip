@@ -1005,6 +1005,18 @@ __device__ __forceinline__ void plane_space(V3 n, V3& p, V3& q) {
     }
 }
 
+/* dot(u, Jv) for the three rows of a point whose normal is (0, 0, 1): plane_space gives
+ * t1 = (0, -1, 0), t2 = (1, -0, -0) for it (v_rsq_f32(1) = 1), so the sums are Jv.z, -Jv.y and
+ * Jv.x, every product exact: a non-zero entry is the sum's word.  A zero entry sums with the two
+ * signed-zero products to +0 unless all three terms are -0, and the 0.0f terms give that +0: on
+ * the lanes past the point's joint (Jv = (+0, +0, +0); a bare -Jv.y would be -0 there) and for a
+ * vertical joint axis (joint 0: Jv.z = 0 dy - 0 dx, of either sign).  The all -0 case needs an
+ * exact zero beside two entries of the right signs; tests/test_gpu_table_normal_bits.py holds the
+ * step's words to those of the three-term sums. */
+__device__ __forceinline__ float up_row_j(int dir, V3 Jv) {
+    return dir == 0 ? Jv.z + 0.0f : (dir == 1 ? 0.0f - Jv.y : Jv.x + 0.0f);
+}
+
 __device__ __forceinline__ bool on_table(const PgxDevEnv& e, float x, float y) {
     return fabsf(x - e.table_cx) <= e.table_hx && fabsf(y - e.table_cy) <= e.table_hy;
 }
@@ -1796,7 +1808,14 @@ __device__ __forceinline__ void cap_ends_own(const M3& Rl, V3 ol, const CapRow& 
  * pair); the row keeps the RB deepest by (depth, discovery order) like g1_insert -- ranked by
  * broadcast only when an env has more -- and every kept candidate goes straight to its id-ordered slot
  * (ids 2c + end grow with the lane), so sort_groups has nothing left to do. */
-template <class LT>
+/* ZN (the arm kernels of the wide layout, no object and no obstacles): every robot point is one of
+ * these, its normal +z, its g1rb 0 and its g1w -1, so the contact part takes the three as constants
+ * (substep_g) and the candidate lane does not store them.  (-DPGX_UP_NORMAL=0: the A/B build that
+ * carries them as data, as every other kernel does.) */
+#ifndef PGX_UP_NORMAL
+#define PGX_UP_NORMAL 1
+#endif
+template <bool ZN = false, class LT>
 __device__ __forceinline__ void robot_table_contacts_g(const PgxDevEnv& e, LT& L, int es, int c, V3 A, V3 B,
                                                        const CapLane& cl, float tt, float tp) {
     const bool on = c < PGX_NCAP && (cl.flags & PGX_CAP_VS_TABLE);
@@ -1830,25 +1849,31 @@ __device__ __forceinline__ void robot_table_contacts_g(const PgxDevEnv& e, LT& L
     const int jc = cl.j;
     if (k0) {
         const int sl = base;
-        L.g1d[sl][es] = d0; L.g1id[sl][es] = (float)(2 * c); L.g1j[sl][es] = jc; L.g1w[sl][es] = -1;
+        L.g1d[sl][es] = d0; L.g1id[sl][es] = (float)(2 * c); L.g1j[sl][es] = jc;
         L.g1p[sl][0][es] = A.x; L.g1p[sl][1][es] = A.y; L.g1p[sl][2][es] = A.z - r;
-        L.g1n[sl][0][es] = 0.0f; L.g1n[sl][1][es] = 0.0f; L.g1n[sl][2][es] = 1.0f;
-        L.g1rb[sl][0][es] = 0.0f; L.g1rb[sl][1][es] = 0.0f; L.g1rb[sl][2][es] = 0.0f;
+        if constexpr (!ZN) {
+            L.g1w[sl][es] = -1;
+            L.g1n[sl][0][es] = 0.0f; L.g1n[sl][1][es] = 0.0f; L.g1n[sl][2][es] = 1.0f;
+            L.g1rb[sl][0][es] = 0.0f; L.g1rb[sl][1][es] = 0.0f; L.g1rb[sl][2][es] = 0.0f;
+        }
     }
     if (k1) {
         const int sl = base + (k0 ? 1 : 0);
-        L.g1d[sl][es] = d1; L.g1id[sl][es] = (float)(2 * c + 1); L.g1j[sl][es] = jc; L.g1w[sl][es] = -1;
+        L.g1d[sl][es] = d1; L.g1id[sl][es] = (float)(2 * c + 1); L.g1j[sl][es] = jc;
         L.g1p[sl][0][es] = B.x; L.g1p[sl][1][es] = B.y; L.g1p[sl][2][es] = B.z - r;
-        L.g1n[sl][0][es] = 0.0f; L.g1n[sl][1][es] = 0.0f; L.g1n[sl][2][es] = 1.0f;
-        L.g1rb[sl][0][es] = 0.0f; L.g1rb[sl][1][es] = 0.0f; L.g1rb[sl][2][es] = 0.0f;
+        if constexpr (!ZN) {
+            L.g1w[sl][es] = -1;
+            L.g1n[sl][0][es] = 0.0f; L.g1n[sl][1][es] = 0.0f; L.g1n[sl][2][es] = 1.0f;
+            L.g1rb[sl][0][es] = 0.0f; L.g1rb[sl][1][es] = 0.0f; L.g1rb[sl][2][es] = 0.0f;
+        }
     }
     L.cnt[1][es] = __builtin_popcount(m0) + __builtin_popcount(m1);
 }
 /* (the end points from the LDS arrays link_capsules fills) */
-template <class LT>
+template <bool ZN = false, class LT>
 __device__ __forceinline__ void robot_table_contacts_g(MRef m, const PgxDevEnv& e, LT& L, int es, int c) {
     const int cc = c < PGX_NCAP ? c : 0;
-    robot_table_contacts_g(e, L, es, c, lds3(L.capA[cc], es), lds3(L.capB[cc], es), cap_lane(), cap_tau<TAU_TABLE>(m, cc),
+    robot_table_contacts_g<ZN>(e, L, es, c, lds3(L.capA[cc], es), lds3(L.capB[cc], es), cap_lane(), cap_tau<TAU_TABLE>(m, cc),
                            cap_tau<TAU_PLANE>(m, cc));
 }
 
@@ -2235,9 +2260,9 @@ __device__ __forceinline__ void substep_dyn_g(MRef m, const PgxDevEnv& e, const 
                 const CapRow cr = cap_row_load(*Lp, c);
                 V3 A, B;
                 cap_ends_own(Rl, ol, cr, A, B);
-                robot_table_contacts_g(e, *Lp, es, c, A, B, cr.cl, cr.tt, cr.tp);
+                robot_table_contacts_g<!AO && PGX_UP_NORMAL>(e, *Lp, es, c, A, B, cr.cl, cr.tt, cr.tp);
             } else {
-                robot_table_contacts_g(m, e, *Lp, es, c);
+                robot_table_contacts_g<!AO && PGX_UP_NORMAL>(m, e, *Lp, es, c);
             }
             if constexpr (AO) {
                 /* obstacle contacts (ao_obstacle_candidates), lane-parallel: per obstacle, lane c
@@ -3139,6 +3164,11 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
     constexpr int CGR = decltype(cgr_c)::value;   /* this instance's register points */
     constexpr bool TWOPT = CGR < CGR_ALL;         /* the two-point instance: no point past CGR in the wave */
     static_assert(!TWOPT || (MERGE_K && CGR == 2), "the two-point instance belongs to the kernels that merge");
+    /* ZN (the arm kernels: no object, no obstacles): every robot point is a capsule end sphere on
+     * the table top or the plane (robot_table_contacts_g<true>), so its normal (0, 0, 1), its g1rb 0
+     * and its g1w -1 are compile-time constants here: not stored by the candidate lane, not read
+     * back, plane_space not evaluated, and the rows' Jacobian entries are up_row_j's */
+    constexpr bool ZN = !OBJ && !AO && PGX_UP_NORMAL;
     constexpr int NP = P0 + (CONT ? CGR : 0);
     constexpr int RB_ALL = CONT ? ContactLdsGT<OBJ, FULL>::RB : CGR_ALL;   /* robot budget: the cache's robot slots */
     constexpr int RB = TWOPT ? CGR : RB_ALL;      /* points CGR..RB-1 are the extra rows */
@@ -3229,7 +3259,7 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
         float gId[CGR], gD[CGR];
         auto read_point = [&](int k) __attribute__((always_inline)) {
             gP[k] = v3(L.g1p[k][0][es], L.g1p[k][1][es], L.g1p[k][2][es]);
-            gN[k] = v3(L.g1n[k][0][es], L.g1n[k][1][es], L.g1n[k][2][es]);
+            gN[k] = ZN ? v3(0.0f, 0.0f, 1.0f) : v3(L.g1n[k][0][es], L.g1n[k][1][es], L.g1n[k][2][es]);
             gRb[k] = OBJ ? v3(L.g1rb[k][0][es], L.g1rb[k][1][es], L.g1rb[k][2][es]) : v3(0.0f, 0.0f, 0.0f);
             gJ[k] = L.g1j[k][es];
             gW[k] = PERS ? L.g1w[k][es] : -1;
@@ -3279,13 +3309,13 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
                 pmu[p] = point_mu<AO, FULL>(m, id);
                 const bool vs_obj = OBJ && id >= kTableIdLimit;
                 const float warm = warm_pt(gW[k], id);
-                V3 t1, t2;
-                plane_space(n, t1, t2);
+                V3 t1 = v3(0.0f, -1.0f, 0.0f), t2 = v3(1.0f, -0.0f, -0.0f);
+                if constexpr (!ZN) plane_space(n, t1, t2);
                 const V3 Jv = (arm && c <= jl) ? cross(zc, P - oc) : v3(0, 0, 0);
 #pragma unroll
                 for (int dir = 0; dir < 3; dir++) {
                     const V3 u = dir == 0 ? n : (dir == 1 ? t1 : t2);
-                    float J = dot(u, Jv);
+                    float J = ZN ? up_row_j(dir, Jv) : dot(u, Jv);
                     if (OBJ) {
                         const V3 ca = cross(rb, u);
                         const float oj = pick_obj(-1.0f * u, -1.0f * ca);
@@ -3342,7 +3372,7 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
                 }
                 const bool a = k < n1;
                 const V3 P = v3(L.g1p[k][0][es], L.g1p[k][1][es], L.g1p[k][2][es]);
-                const V3 n = v3(L.g1n[k][0][es], L.g1n[k][1][es], L.g1n[k][2][es]);
+                const V3 n = ZN ? v3(0.0f, 0.0f, 1.0f) : v3(L.g1n[k][0][es], L.g1n[k][1][es], L.g1n[k][2][es]);
                 const V3 rb = v3(L.g1rb[k][0][es], L.g1rb[k][1][es], L.g1rb[k][2][es]);
                 const int jl = L.g1j[k][es];
                 const float id = L.g1id[k][es];
@@ -3350,14 +3380,14 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
                 const int wk = PERS ? L.g1w[k][es] : -1;
                 const float warm = (PERS && wk >= 0) ? m.warmstart * L.mimp[wk < 0 ? 0 : wk][es]
                                                      : warm_lookup<RB>(L, es, CACHE1, id, m.warmstart);
-                V3 t1, t2;
-                plane_space(n, t1, t2);
+                V3 t1 = v3(0.0f, -1.0f, 0.0f), t2 = v3(1.0f, -0.0f, -0.0f);
+                if constexpr (!ZN) plane_space(n, t1, t2);
                 const V3 Jv = (arm && c <= jl) ? cross(zc, P - oc) : v3(0, 0, 0);
                 float jinv_n = 0.0f;
 #pragma unroll
                 for (int dir = 0; dir < 3; dir++) {
                     const V3 u = dir == 0 ? n : (dir == 1 ? t1 : t2);
-                    float J = dot(u, Jv);
+                    float J = ZN ? up_row_j(dir, Jv) : dot(u, Jv);
                     if (OBJ) {
                         const V3 ca = cross(rb, u);
                         const float oj = pick_obj(-1.0f * u, -1.0f * ca);
@@ -3952,6 +3982,43 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
         else resid = fmaxf(resid, fabsf(delta));
     };
     static_assert(limit_rows_paired(), "limit rows come as (lower, upper) pairs of one dof after the motor rows");
+    /* ROT (the merged sweeps): the row that leads a half-sweep, split into its head -- x and delta',
+     * which write no state -- and its commit (bounds / lambda', gv, the residual's start: mrow's and
+     * srow's arithmetic for a merged first row, mg_c = 2).  solve() computes the head of the next
+     * half-sweep's first row before the exit test of the one that ends, so the chain's first two
+     * links (the DPP-sourced subtract of the gv the last row just wrote, med3) run in the shadow of
+     * max3 -> v_cmp -> mask -> branch instead of behind it; on exit the two instructions are
+     * discarded.  The leaders: a motor row (row 0 forward, the last motor row reversed) or, in the
+     * partial mode's reversed half, the last slot's upper limit row; a contact row never leads.
+     * (-DPGX_ROT=0: the A/B build with the heads behind the branch.) */
+#ifndef PGX_ROT
+#define PGX_ROT 1
+#endif
+    auto mrow_head = [&](auto rc) __attribute__((always_inline)) {
+        constexpr int r = decltype(rc)::value, d = kPgxRowCode[r] & 15;
+        static_assert((kPgxRowCode[r] >> 4) == 0, "a motor row leads");
+        float delta = __builtin_amdgcn_fmed3f(rhs[r] - bcast16<d>(gv), bnd[d].x, bnd[d].y);
+        asm volatile("" : "+v"(delta));   /* stays ahead of the exit branch (else sunk behind it, its only user) */
+        return delta;
+    };
+    auto mrow_commit = [&](auto rc, float delta, float& resid) __attribute__((always_inline)) {
+        constexpr int d = kPgxRowCode[decltype(rc)::value] & 15;
+        bnd[d] -= (f2){delta, delta};
+        gv += mcs[d] * delta;
+        resid = fabsf(delta);
+    };
+    auto srow_head = [&](auto sc) __attribute__((always_inline)) {   /* the slot's upper row */
+        constexpr int S = decltype(sc)::value;
+        float delta = __builtin_amdgcn_fmed3f(srh[S][1] + bcast16<SL0 + S>(gv), -slam[S][1], slhi[S] - slam[S][1]);
+        asm volatile("" : "+v"(delta));
+        return delta;
+    };
+    auto srow_commit = [&](auto sc, float delta, float& resid) __attribute__((always_inline)) {
+        constexpr int S = decltype(sc)::value;
+        slam[S][1] += delta;
+        gv += smcs[S] * -delta;
+        resid = fabsf(delta);
+    };
     auto solve = [&](auto mode_c, auto nw_c, auto k_c, auto nx_c, auto mg_c) __attribute__((always_inline)) {
         constexpr int MODE = decltype(mode_c)::value;   /* 0 far, 1 speculative, 2 all rows, 3 partial */
         constexpr int NW = decltype(nw_c)::value;
@@ -3962,6 +4029,56 @@ __device__ __forceinline__ bool substep_g(MPtr mp, const PgxDevEnv& e, float* q,
         constexpr bool MG = decltype(mg_c)::value != 0;
         const IC<MG ? 2 : 0> mgf_c{};   /* the half-sweep's first row (res_acc) */
         constexpr int LASTM = last_motor_row();
+        if constexpr (MERGE && MG && PGX_ROT) {
+            /* the rotated loop: the same rows in the same order, each half-sweep's first row as
+             * commit (here) and head (before the exit test of the half-sweep ahead of it) */
+            static_assert(MODE == 1 || (MODE == 3 && K >= 1), "merged sweeps: the speculative and the partial solve");
+            auto head_rev = [&]() __attribute__((always_inline)) {
+                if constexpr (MODE == 3) return srow_head(IC<K - 1>{});
+                else return mrow_head(IC<LASTM>{});
+            };
+            float hd = head_rev();
+            for (int it = 0; it < n_it; it += 2) {
+                float resid;
+                limit_check();
+                if constexpr (MODE == 3) {   /* the limit block leads the reversed sweep */
+                    sfor<0, K>([&](auto i) __attribute__((always_inline)) {
+                        constexpr int S = K - 1 - decltype(i)::value;
+                        if constexpr (S == K - 1) srow_commit(IC<S>{}, hd, resid);
+                        else srow(IC<S>{}, IC<2>{}, g2_c, mg_c, resid);
+                        srow(IC<S>{}, IC<1>{}, g2_c, mg_c, resid);
+                        limit_check();
+                    });
+                }
+                sfor<0, PGX_N_ROWS>([&](auto i) __attribute__((always_inline)) {
+                    constexpr int r = PGX_N_ROWS - 1 - decltype(i)::value;
+                    if constexpr (MODE != 3 && r == LASTM) mrow_commit(IC<r>{}, hd, resid);
+                    else if constexpr ((kPgxRowCode[r] >> 4) == 0) mrow(IC<r>{}, g2_c, mg_c, resid);
+                });
+                contact_rows(nw_c, nx_c, g2_c, mg_c, resid);
+                PGX_PROF_SWEEP();
+                hd = mrow_head(IC<0>{});
+                if (resid <= res_thr || it + 1 >= n_it) break;
+                sfor<0, PGX_N_ROWS>([&](auto i) __attribute__((always_inline)) {
+                    constexpr int r = decltype(i)::value;
+                    if constexpr (r == 0) mrow_commit(IC<r>{}, hd, resid);
+                    else if constexpr ((kPgxRowCode[r] >> 4) == 0) mrow(IC<r>{}, g2_c, mg_c, resid);
+                });
+                limit_check();
+                if constexpr (MODE == 3) {
+                    sfor<0, K>([&](auto sc) __attribute__((always_inline)) {
+                        srow(sc, IC<1>{}, g2_c, mg_c, resid);
+                        srow(sc, IC<2>{}, g2_c, mg_c, resid);
+                        limit_check();
+                    });
+                }
+                contact_rows(nw_c, nx_c, g2_c, mg_c, resid);
+                PGX_PROF_SWEEP();
+                hd = head_rev();
+                if (resid <= res_thr) break;
+            }
+            return;
+        }
         for (int it = 0; it < n_it; it += 2) {
             float resid = 0.0f;
             if constexpr (MODE == 1 || MODE == 3) limit_check();
