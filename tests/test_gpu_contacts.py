@@ -110,6 +110,7 @@ def _one_step_errors(pg, oracle, env_id, n, steps, seed, actions=None, lanes=0, 
         out = ref.step(a.cpu().numpy())
         o32 = r32.step(a.cpu().numpy()) if r32 is not None else None
         obs, ag, dg = _obs(venv)
+        assert np.all(np.isfinite(obs)), t   # before any percentile or mask: a NaN compares false
         if over is not None:   # envs whose last substep held more than 4 robot points
             over[0] += int(((venv.state()["contacts"][2 * n_obj::2] >= 0).sum(dim=0) > 4).sum().item())
         assert np.array_equal(venv.truncated.cpu().numpy(), out["truncated"]), t
@@ -631,6 +632,10 @@ def test_object_kernel_points_past_the_register_budget(pg, oracle):
     held = (small.state()["contacts"][2 * orc.OBJECT_POINTS::2] >= 0).sum(0).cpu().numpy()
     assert held.max() > 6, held                        # the step ran rows past the register budget
     obs, ag = small.obs.cpu().numpy(), small.achieved_goal.cpu().numpy()
+    # the screen below (> 1e-4) is false for NaN: finite first, the observation and the state behind it
+    assert np.all(np.isfinite(obs)) and np.all(np.isfinite(ag))
+    for k in ("q", "qd", "qc", "object"):
+        assert bool(torch.isfinite(small.state()[k]).all()), k
     e_ee = np.abs(obs[:, :3] - out["obs"][:, :3]).max(axis=1)
     e_ag = np.abs(ag - out["ag"]).max(axis=1)
     print(f"\n{m} envs past six robot points (held {held.tolist()}): max |ee| {e_ee.max():.2e}, |object| {e_ag.max():.2e}")
